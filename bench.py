@@ -13,6 +13,12 @@ N>1 is launched by the driver as
 (one rank per GPU over RCCL; RANK/WORLD_SIZE read from the env).
 One bench "step" = one full generation of the global batch (plan ->
 CLIP encode -> 20-step denoise -> VAE decode -> image gather).
+
+A plain run sets up, warms up, times the K steps and prints one JSON result
+line. --dump-outputs DIR additionally writes the last timed step's gallery
+(images.npy, seeds.npy) so two builds can be compared output for output;
+the request and its seeds are fixed, so inputs are identical run to run.
+--full is where secondary measurements live (none today).
 """
 from __future__ import annotations
 
@@ -23,6 +29,33 @@ import sys
 import time
 
 import torch
+
+
+# --dump-outputs budget: the gallery is written whole when it fits, else as
+# a fixed, seeded sample of its elements (same indices on every run, so two
+# builds compare element for element)
+DUMP_MAX_ELEMS = 4 * 1024 * 1024  # float32 -> 16 MiB
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir: str, res) -> None:
+    """Write the GalleryResult of the last timed step as .npy files:
+    images.npy (float32; the uint8 gallery [N,H,W,3] flattened, or a seeded
+    sample of it) and seeds.npy (float64, one per gallery image)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    flat = res.images.reshape(-1).numpy()
+    if flat.size > DUMP_MAX_ELEMS:
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        idx = rng.integers(0, flat.size, size=DUMP_MAX_ELEMS)
+        flat = flat[idx]
+        images = flat.astype(np.float32)
+    else:
+        images = res.images.numpy().astype(np.float32)
+    np.save(os.path.join(out_dir, "images.npy"), images)
+    np.save(os.path.join(out_dir, "seeds.npy"),
+            np.asarray(res.seeds, dtype=np.float64))
 
 
 def main() -> int:
@@ -40,7 +73,18 @@ def main() -> int:
     ap.add_argument("--task", choices=["txt2img", "img2img"], default="txt2img",
                     help="img2img adds VAE encode + strength-limited denoise")
     ap.add_argument("--strength", type=float, default=0.75)
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed "
+                         "step returned to DIR/<name>.npy (float32/float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements; a plain run "
+                         "does only what the headline figure needs (today "
+                         "the benchmark has none, so this adds nothing)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
 
     from sdwd_amd.config import add_flags  # noqa: F401  (flag surface)
     from sdwd_amd.parallel import DistributedEngine, GenerationRequest, barrier
@@ -100,6 +144,9 @@ def main() -> int:
 
     all_elapsed = allgather_floats([elapsed], dev if have_gpu else "cpu")
     elapsed = max(v[0] for v in all_elapsed)
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
 
     if rank == 0:
         total_images = args.global_batch * args.steps
