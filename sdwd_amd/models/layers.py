@@ -69,7 +69,9 @@ class SDConv2d(nn.Conv2d):
       the implicit-GEMM MFMA kernel (ops/hip/conv.hip), with bias and an
       optional residual add fused into the epilogue;
     * 1x1 stride-1 on GPU -> a hipBLASLt GEMM over the NHWC rows;
-    * everything else (stem convs, CPU) -> F.conv2d (MIOpen / native).
+    * 3x3 pad-1 with Cin 3/4/9 (the stem/IO convs) on GPU -> the direct
+      small-Cin kernel (ops/hip/conv_small.hip);
+    * everything else (CPU, other shapes) -> F.conv2d (MIOpen / native).
     """
 
     def __init__(self, *args, **kwargs):

@@ -251,7 +251,9 @@ def scale(x: torch.Tensor, c: float) -> torch.Tensor:
     return (c * x.float()).to(x.dtype)
 
 
-def _attach_gn_partials(y: torch.Tensor, gnp: torch.Tensor) -> None:
+def _attach_gn_partials(
+    y: torch.Tensor, gnp: Optional[torch.Tensor]
+) -> None:
     """Ride the conv's per-tile (sum, sumsq) side-channel on the output
     tensor; a downstream GroupNorm consumes it and skips its stats read.
     The _version pin invalidates the cache if y is ever mutated in place."""
@@ -280,6 +282,29 @@ def cat_channels_gn(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# conv3x3 kernel variants -> the extension's `force` argument
+_CONV_FORCE = {"auto": 0, "v2": 2, "v4": 4}
+_CONV_ENV_FORCE: Optional[int] = None
+
+
+def _conv_force(variant: Optional[str]) -> int:
+    """None -> SDWD_CONV (read once, unknown values mean auto); an explicit
+    variant always wins and must be one of auto/v2/v4."""
+    global _CONV_ENV_FORCE
+    if variant is None:
+        if _CONV_ENV_FORCE is None:
+            _CONV_ENV_FORCE = _CONV_FORCE.get(
+                os.environ.get("SDWD_CONV", ""), 0
+            )
+        return _CONV_ENV_FORCE
+    if variant not in _CONV_FORCE:
+        raise ValueError(
+            f"conv3x3: unknown variant {variant!r} "
+            f"(expected one of {sorted(_CONV_FORCE)})"
+        )
+    return _CONV_FORCE[variant]
+
+
 def conv3x3(
     x: torch.Tensor,
     w_prep: torch.Tensor,
@@ -288,19 +313,22 @@ def conv3x3(
     stride: int = 1,
     chan_bias: Optional[torch.Tensor] = None,
     collect_gn: bool = False,
+    variant: Optional[str] = None,
 ) -> torch.Tensor:
     """NHWC implicit-GEMM 3x3 conv (pad 1); bias, an optional residual and
     an optional per-(sample, channel) bias (the ResBlock time-embedding
     projection) all fused into the epilogue. With collect_gn the epilogue
     also emits per-tile GroupNorm partial sums (see _attach_gn_partials).
+    variant picks the kernel: "auto" is the measured dispatch
+    (ext().conv3x3_plan), "v2" the 128-tile kernel everywhere, "v4" the
+    256x256 pipeline on every legal shape; None follows SDWD_CONV.
     GPU-only entry."""
-    if collect_gn:
-        y, gnp = ext().conv3x3_nhwc_gn(
-            x, w_prep, bias, residual, chan_bias, stride
-        )
-        _attach_gn_partials(y, gnp)
-        return y
-    return ext().conv3x3_nhwc(x, w_prep, bias, residual, chan_bias, stride)
+    y, gnp = ext().conv3x3_nhwc(
+        x, w_prep, bias, residual, chan_bias, stride, collect_gn,
+        _conv_force(variant),
+    )
+    _attach_gn_partials(y, gnp)
+    return y
 
 
 def conv3x3_small(
@@ -332,11 +360,9 @@ def ups2x_conv3x3(
 ) -> torch.Tensor:
     """Nearest-2x upsample fused into a 3x3 conv (VAE decoder / UNet
     Upsample): no 4x intermediate tensor. GPU-only entry."""
-    if collect_gn:
-        y, gnp = ext().ups2x_conv3x3_gn(x, w_prep, bias)
-        _attach_gn_partials(y, gnp)
-        return y
-    return ext().ups2x_conv3x3(x, w_prep, bias)
+    y, gnp = ext().ups2x_conv3x3(x, w_prep, bias, collect_gn)
+    _attach_gn_partials(y, gnp)
+    return y
 
 
 # ---------------------------------------------------------------------------

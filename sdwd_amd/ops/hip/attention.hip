@@ -573,7 +573,7 @@ bool flash_supported(long d_head) {
   return d_head > 16 && d_head <= 192 && (d_head % 8) == 0;
 }
 
-#if defined(__HIP_PLATFORM_AMD__) && !defined(SDWD_NO_TORCH)
+#ifdef __HIP_PLATFORM_AMD__
 static inline long round16(long d) { return (d + 15) / 16 * 16; }
 
 // qkv layout: "bhsd" (q.size = [B,H,S,D]) or "bshd" ([B,S,H,D]); tensors

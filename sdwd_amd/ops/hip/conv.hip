@@ -22,9 +22,12 @@
 //  * bias, per-(sample,channel) bias (time embedding) and the ResBlock
 //    residual add are fused into the epilogue.
 //
-// Requirements: Cin % 64 == 0 (every SD1.5/SDXL/VAE hot shape; small-Cin
-// stem convs stay on MIOpen), any Cout, stride 1 or 2, pad 1, kernel 3x3.
+// Requirements: Cin % 64 == 0 (every SD1.5/SDXL/VAE hot shape; the small-Cin
+// stem convs go to conv_small.hip), any Cout, stride 1 or 2, pad 1, kernel 3x3.
 #include "common.h"
+#include <map>
+#include <mutex>
+#include <tuple>
 
 typedef __attribute__((ext_vector_type(4))) float f32x4c;
 
@@ -281,105 +284,18 @@ __launch_bounds__(256, 2) __global__ void conv3x3_nhwc_bf16_kernel(
 #ifdef __HIP_PLATFORM_AMD__
 bool conv3x3_supported(long cin) { return cin % 64 == 0 && cin >= 64; }
 
-torch::Tensor conv3x3_nhwc_impl(torch::Tensor x, torch::Tensor w_prep,
-                                c10::optional<torch::Tensor> bias,
-                                c10::optional<torch::Tensor> residual,
-                                c10::optional<torch::Tensor> chan_bias,
-                                long stride, torch::Tensor *gnp_out) {
-  // x: [N,C,H,W] channels_last; w_prep: [Cout,3,3,Cin] contiguous
-  TORCH_CHECK(x.is_contiguous(torch::MemoryFormat::ChannelsLast),
-              "conv3x3: x must be channels_last");
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16);
-  const int N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
-  const int Cout = w_prep.size(0);
-  TORCH_CHECK(conv3x3_supported(Cin), "conv3x3: Cin % 64 != 0");
-  const int Ho = (H + 2 - 3) / stride + 1;
-  const int Wo = (W + 2 - 3) / stride + 1;
-  auto y = torch::empty({N, Cout, Ho, Wo},
-                        x.options().memory_format(
-                            torch::MemoryFormat::ChannelsLast));
-  static torch::Tensor zero_page;
-  if (!zero_page.defined() || zero_page.device() != x.device())
-    zero_page = torch::zeros({64}, x.options());
-  const long M = (long)N * Ho * Wo;
+// Which kernel serves which output columns: {number of full 256-column
+// tiles on the v4 kernel, remainder columns on the v2 kernel, remainder
+// uses BN=64 (false when there is no remainder)}. force: 0 = measured
+// policy, 2 = v2 everywhere, 4 = v4 on every legal shape (A/B tooling).
+// The launcher below follows this and nothing else decides.
+std::tuple<long, long, bool> conv3x3_plan(long N, long H, long W, long Cin,
+                                          long Cout, long stride,
+                                          long force) {
+  const long Ho = (H + 2 - 3) / stride + 1;
+  const long Wo = (W + 2 - 3) / stride + 1;
+  const long M = N * Ho * Wo;
   const long mtiles = (M + CONV_BM - 1) / CONV_BM;
-  dim3 grid((unsigned)((Cout + CONV_BN - 1) / CONV_BN),
-            (unsigned)std::min<long>(mtiles, 32768),
-            (unsigned)((mtiles + 32767) / 32768));
-  dim3 block(256);
-  const bool has_b = bias.has_value();
-  const bool has_r = residual.has_value();
-  torch::Tensor bf32;
-  const float *bptr = nullptr;
-  if (has_b) {
-    bf32 = bias->to(torch::kFloat).contiguous();
-    bptr = bf32.data_ptr<float>();
-  }
-  const __hip_bfloat16 *rptr = nullptr;
-  if (has_r) {
-    TORCH_CHECK(
-        residual->is_contiguous(torch::MemoryFormat::ChannelsLast));
-    rptr = (const __hip_bfloat16 *)residual->data_ptr();
-  }
-  const bool has_cb = chan_bias.has_value();
-  torch::Tensor cbt;
-  const __hip_bfloat16 *cbptr = nullptr;
-  if (has_cb) {
-    cbt = chan_bias->to(torch::kBFloat16).contiguous();
-    cbptr = (const __hip_bfloat16 *)cbt.data_ptr();
-  }
-  auto stream = cur_stream();
-  // GroupNorm partial side-channel (one (sum,sumsq) pair per 128-row tile
-  // per channel): only when every 128-row tile lies inside one image
-  float *gnp_ptr = nullptr;
-  if (gnp_out != nullptr && ((long)Ho * Wo) % 128 == 0) {
-    *gnp_out = torch::empty(
-        {M / 128, 2, (long)Cout},
-        x.options().dtype(torch::kFloat));
-    gnp_ptr = gnp_out->data_ptr<float>();
-  }
-  // v2 (2 blocks/CU, 2-buffer glds) measured faster than the deeper v3
-  // pipeline (18.8 vs 21.1 ms on the shape set): at 2 blocks/CU the
-  // block-level overlap already hides the DMA. v3 stays opt-in.
-  static const bool use_v3 = getenv("SDWD_CONV_V3") != nullptr;
-  if (use_v3) {
-    // v3: deep-pipelined 256x128 tile (conv_v3.hip)
-    const long mt3 = (M + 255) / 256;
-    dim3 g3((unsigned)((Cout + 127) / 128),
-            (unsigned)std::min<long>(mt3, 32768),
-            (unsigned)((mt3 + 32767) / 32768));
-    dim3 b3(512);
-#define PICK3(B_, R_, C_) conv3x3_v3_kernel<B_, R_, C_>
-    auto k3 = has_b ? (has_r ? (has_cb ? PICK3(true, true, true)
-                                       : PICK3(true, true, false))
-                             : (has_cb ? PICK3(true, false, true)
-                                       : PICK3(true, false, false)))
-                    : (has_r ? (has_cb ? PICK3(false, true, true)
-                                       : PICK3(false, true, false))
-                             : (has_cb ? PICK3(false, false, true)
-                                       : PICK3(false, false, false)));
-#undef PICK3
-    hipLaunchKernelGGL(k3, g3, b3, 0, stream,
-                       (const __hip_bfloat16 *)x.data_ptr(),
-                       (const __hip_bfloat16 *)w_prep.data_ptr(), bptr, rptr,
-                       cbptr,
-                       (const __hip_bfloat16 *)zero_page.data_ptr(),
-                       (__hip_bfloat16 *)y.data_ptr(), N, H, W, Cin, Cout,
-                       Ho, Wo, (int)stride);
-    return y;
-  }
-  // v4: the 256x256 8-phase deep pipeline serves full 256-column tiles;
-  // the v2 128-tile kernel covers the Cout remainder (e.g. 320 = 256+64).
-  // SDWD_CONV=v2 forces the round-1 kernel everywhere; =v4 forces the
-  // deep pipeline on every legal shape (A/B tooling).
-  static const int conv_force = [] {
-    const char *e = getenv("SDWD_CONV");
-    if (!e) return 0;
-    if (strcmp(e, "v2") == 0) return 2;
-    if (strcmp(e, "v4") == 0) return 4;
-    return 0;
-  }();
-  const bool v2only = conv_force == 2;
   const long mt4 = (M + V4_BM - 1) / V4_BM;
   // measured winners (profiles/r02_conv_family.md): the 256x256 pipeline
   // wins on the SD-UNet level-0/1 shapes (Cin<=960, Cout<=640, big M) and
@@ -390,151 +306,181 @@ torch::Tensor conv3x3_nhwc_impl(torch::Tensor x, torch::Tensor w_prep,
   // 256 CUs (small shards at N=8 under-fill 256-row tiles: the 128-row
   // v2 kernel at 2 blocks/CU wins there)
   const bool v4_shape =
-      conv_force == 4
-          ? (Cin % 64 == 0 && Cout >= 256)
-          : (Cin <= 960 && Cout <= 640 && Cout >= 256 &&
-             ((M + V4_BM - 1) / V4_BM) * (Cout / 256) >= 256);
-  const long nfull = (v2only || !v4_shape) ? 0 : Cout / 256;
-  const int rem = (int)(Cout - nfull * 256);
+      force == 4 ? (Cin % 64 == 0 && Cout >= 256)
+                 : (Cin <= 960 && Cout <= 640 && Cout >= 256 &&
+                    mt4 * (Cout / 256) >= 256);
+  const long nfull = (force == 2 || !v4_shape) ? 0 : Cout / 256;
+  const long rem = Cout - nfull * 256;
+  // BN=64 when the remainder is one 64-tile OR when the BN=128 grid
+  // would under-fill the 256 CUs (small shards: twice the blocks beat
+  // the halved B-reuse when occupancy-starved)
+  const bool bn64 =
+      rem > 0 && (rem <= 64 || mtiles * ((rem + 127) / 128) < 512);
+  return {nfull, rem, bn64};
+}
+
+// The padding rows' zero page: one 64-element tensor per device ordinal,
+// created on first use and kept for the life of the process.
+static const __hip_bfloat16 *zero_page_for(const torch::Tensor &x) {
+  static std::mutex mu;
+  static std::map<int, torch::Tensor> pages;
+  std::lock_guard<std::mutex> lock(mu);
+  auto &page = pages[x.get_device()];
+  if (!page.defined()) page = torch::zeros({64}, x.options());
+  return (const __hip_bfloat16 *)page.data_ptr();
+}
+
+// Call f with one std::bool_constant per runtime bool, so a generic lambda
+// can name the kernel instantiation: dispatch_bools(f, a, b) ends in
+// f(bool_constant<a>{}, bool_constant<b>{}).
+template <class F>
+static void dispatch_bools(F &&f) {
+  f();
+}
+template <class F, class... Rest>
+static void dispatch_bools(F &&f, bool b, Rest... rest) {
+  if (b)
+    dispatch_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+  else
+    dispatch_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
+
+// M tiles ride grid y, with the overflow past 32768 in z
+static dim3 conv_grid(long col_tiles, long mtiles) {
+  return dim3((unsigned)col_tiles, (unsigned)std::min<long>(mtiles, 32768),
+              (unsigned)((mtiles + 32767) / 32768));
+}
+
+// What the plain and the fused-upsample entry share: checks, output and
+// GroupNorm-partial allocation, and the operand pointers. The tensors are
+// members so the fp32 bias / bf16 chan-bias copies outlive the launch call.
+struct ConvArgs {
+  int N, Cin, H, W, Cout, Ho, Wo;
+  long M;
+  torch::Tensor y, gnp, bias_f32, cb_bf16;
+  const __hip_bfloat16 *x, *w, *res = nullptr, *cb = nullptr, *zero;
+  const float *bias = nullptr;
+  __hip_bfloat16 *yp;
+  float *gnp_ptr = nullptr;
+
+  // x: [N,C,H,W] channels_last; w_prep: [Cout,3,3,Cin] contiguous
+  ConvArgs(const torch::Tensor &xt, const torch::Tensor &w_prep,
+           const c10::optional<torch::Tensor> &bias_t,
+           const c10::optional<torch::Tensor> &residual,
+           const c10::optional<torch::Tensor> &chan_bias, int Ho_, int Wo_,
+           bool collect_gn)
+      : N(xt.size(0)), Cin(xt.size(1)), H(xt.size(2)), W(xt.size(3)),
+        Cout(w_prep.size(0)), Ho(Ho_), Wo(Wo_), M((long)N * Ho_ * Wo_) {
+    TORCH_CHECK(xt.is_contiguous(torch::MemoryFormat::ChannelsLast),
+                "conv3x3: x must be channels_last");
+    TORCH_CHECK(xt.scalar_type() == torch::kBFloat16);
+    TORCH_CHECK(conv3x3_supported(Cin), "conv3x3: Cin % 64 != 0");
+    y = torch::empty({N, Cout, Ho, Wo},
+                     xt.options().memory_format(
+                         torch::MemoryFormat::ChannelsLast));
+    x = (const __hip_bfloat16 *)xt.data_ptr();
+    w = (const __hip_bfloat16 *)w_prep.data_ptr();
+    yp = (__hip_bfloat16 *)y.data_ptr();
+    zero = zero_page_for(xt);
+    if (bias_t.has_value()) {
+      bias_f32 = bias_t->to(torch::kFloat).contiguous();
+      bias = bias_f32.data_ptr<float>();
+    }
+    if (residual.has_value()) {
+      TORCH_CHECK(
+          residual->is_contiguous(torch::MemoryFormat::ChannelsLast));
+      res = (const __hip_bfloat16 *)residual->data_ptr();
+    }
+    if (chan_bias.has_value()) {
+      cb_bf16 = chan_bias->to(torch::kBFloat16).contiguous();
+      cb = (const __hip_bfloat16 *)cb_bf16.data_ptr();
+    }
+    // GroupNorm partial side-channel (one (sum,sumsq) pair per 128-row
+    // tile per channel): only when every 128-row tile lies inside one image
+    if (collect_gn && ((long)Ho * Wo) % 128 == 0) {
+      gnp = torch::empty({M / 128, 2, (long)Cout},
+                         xt.options().dtype(torch::kFloat));
+      gnp_ptr = gnp.data_ptr<float>();
+    }
+  }
+
+  std::tuple<torch::Tensor, c10::optional<torch::Tensor>> result() const {
+    if (gnp.defined()) return {y, gnp};
+    return {y, c10::nullopt};
+  }
+};
+
+// returns (y, GroupNorm partials or None)
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> conv3x3_nhwc(
+    torch::Tensor x, torch::Tensor w_prep, c10::optional<torch::Tensor> bias,
+    c10::optional<torch::Tensor> residual,
+    c10::optional<torch::Tensor> chan_bias, long stride, bool collect_gn,
+    long force) {
+  const int Ho = (x.size(2) + 2 - 3) / stride + 1;
+  const int Wo = (x.size(3) + 2 - 3) / stride + 1;
+  ConvArgs a(x, w_prep, bias, residual, chan_bias, Ho, Wo, collect_gn);
+  auto stream = cur_stream();
+  // v4: the 256x256 8-phase deep pipeline serves full 256-column tiles;
+  // the v2 128-tile kernel covers the Cout remainder (e.g. 320 = 256+64).
+  const auto [nfull, rem, bn64] =
+      conv3x3_plan(a.N, a.H, a.W, a.Cin, a.Cout, stride, force);
   if (nfull > 0) {
-    dim3 g4((unsigned)nfull, (unsigned)std::min<long>(mt4, 32768),
-            (unsigned)((mt4 + 32767) / 32768));
-    dim3 b4(512);
-#define PICK4(B_, R_, C_) conv3x3_v4_kernel<B_, R_, C_>
-    auto k4 = has_b ? (has_r ? (has_cb ? PICK4(true, true, true)
-                                       : PICK4(true, true, false))
-                             : (has_cb ? PICK4(true, false, true)
-                                       : PICK4(true, false, false)))
-                    : (has_r ? (has_cb ? PICK4(false, true, true)
-                                       : PICK4(false, true, false))
-                             : (has_cb ? PICK4(false, false, true)
-                                       : PICK4(false, false, false)));
-#undef PICK4
-    hipLaunchKernelGGL(k4, g4, b4, 0, stream,
-                       (const __hip_bfloat16 *)x.data_ptr(),
-                       (const __hip_bfloat16 *)w_prep.data_ptr(), bptr,
-                       rptr, cbptr,
-                       (const __hip_bfloat16 *)zero_page.data_ptr(),
-                       (__hip_bfloat16 *)y.data_ptr(), N, H, W, Cin,
-                       (int)(nfull * 256), Cout, Ho, Wo, (int)stride,
-                       gnp_ptr);
+    const int cols = (int)(nfull * 256);
+    dispatch_bools(
+        [&, cols](auto B, auto R, auto C) {
+          hipLaunchKernelGGL(
+              (conv3x3_v4_kernel<decltype(B)::value, decltype(R)::value,
+                                 decltype(C)::value>),
+              conv_grid(cols / 256, (a.M + V4_BM - 1) / V4_BM), dim3(512), 0,
+              stream, a.x, a.w, a.bias, a.res, a.cb, a.zero, a.yp, a.N, a.H,
+              a.W, a.Cin, cols, a.Cout, a.Ho, a.Wo, (int)stride, a.gnp_ptr);
+        },
+        a.bias != nullptr, a.res != nullptr, a.cb != nullptr);
   }
   if (rem > 0) {
     const long co0 = nfull * 256;
-    // BN=64 when the remainder is one 64-tile OR when the BN=128 grid
-    // would under-fill the 256 CUs (small shards: twice the blocks beat
-    // the halved B-reuse when occupancy-starved)
-    const bool bn64 =
-        rem <= 64 || mtiles * ((rem + 127) / 128) < 512;
-#define PICK(B_, R_, C_)                                              \
-  (bn64 ? conv3x3_nhwc_bf16_kernel<B_, R_, C_, 64>                    \
-        : conv3x3_nhwc_bf16_kernel<B_, R_, C_, 128>)
-    auto kern =
-        has_b ? (has_r ? (has_cb ? PICK(true, true, true)
-                                 : PICK(true, true, false))
-                       : (has_cb ? PICK(true, false, true)
-                                 : PICK(true, false, false)))
-              : (has_r ? (has_cb ? PICK(false, true, true)
-                                 : PICK(false, true, false))
-                       : (has_cb ? PICK(false, false, true)
-                                 : PICK(false, false, false)));
-#undef PICK
-    dim3 g2((unsigned)((rem + (bn64 ? 63 : 127)) / (bn64 ? 64 : 128)),
-            grid.y, grid.z);
-    hipLaunchKernelGGL(
-        kern, g2, block, 0, stream, (const __hip_bfloat16 *)x.data_ptr(),
-        (const __hip_bfloat16 *)w_prep.data_ptr() + co0 * 9 * Cin,
-        bptr ? bptr + co0 : nullptr,
-        rptr ? rptr + co0 : nullptr, cbptr ? cbptr + co0 : nullptr,
-        (const __hip_bfloat16 *)zero_page.data_ptr(),
-        (__hip_bfloat16 *)y.data_ptr() + co0, N, H, W, Cin, rem, Ho, Wo,
-        (int)stride, Cout, gnp_ptr ? gnp_ptr + co0 : nullptr);
+    const int cols = (int)rem;
+    dispatch_bools(
+        [&, co0, cols](auto B, auto R, auto C, auto N64) {
+          constexpr int BN = decltype(N64)::value ? 64 : 128;
+          hipLaunchKernelGGL(
+              (conv3x3_nhwc_bf16_kernel<decltype(B)::value,
+                                        decltype(R)::value,
+                                        decltype(C)::value, BN>),
+              conv_grid((cols + BN - 1) / BN,
+                        (a.M + CONV_BM - 1) / CONV_BM),
+              dim3(256), 0, stream, a.x, a.w + co0 * 9 * a.Cin,
+              a.bias ? a.bias + co0 : nullptr, a.res ? a.res + co0 : nullptr,
+              a.cb ? a.cb + co0 : nullptr, a.zero, a.yp + co0, a.N, a.H, a.W,
+              a.Cin, cols, a.Ho, a.Wo, (int)stride, a.Cout,
+              a.gnp_ptr ? a.gnp_ptr + co0 : nullptr);
+        },
+        a.bias != nullptr, a.res != nullptr, a.cb != nullptr, bn64);
   }
-  return y;
+  return a.result();
 }
 
-torch::Tensor conv3x3_nhwc(torch::Tensor x, torch::Tensor w_prep,
-                           c10::optional<torch::Tensor> bias,
-                           c10::optional<torch::Tensor> residual,
-                           c10::optional<torch::Tensor> chan_bias,
-                           long stride) {
-  return conv3x3_nhwc_impl(x, w_prep, bias, residual, chan_bias, stride,
-                           nullptr);
-}
-
-std::vector<torch::Tensor> conv3x3_nhwc_gn(
-    torch::Tensor x, torch::Tensor w_prep,
-    c10::optional<torch::Tensor> bias,
-    c10::optional<torch::Tensor> residual,
-    c10::optional<torch::Tensor> chan_bias, long stride) {
-  torch::Tensor gnp;
-  auto y = conv3x3_nhwc_impl(x, w_prep, bias, residual, chan_bias, stride,
-                             &gnp);
-  if (!gnp.defined()) gnp = torch::empty({0});
-  return {y, gnp};
-}
-
-torch::Tensor ups2x_conv3x3_impl(torch::Tensor x, torch::Tensor w_prep,
-                                 c10::optional<torch::Tensor> bias,
-                                 torch::Tensor *gnp_out) {
-  // nearest-2x upsample fused into the 3x3 conv (VAE decoder / UNet
-  // Upsample blocks): output is [N, Cout, 2H, 2W]
-  TORCH_CHECK(x.is_contiguous(torch::MemoryFormat::ChannelsLast));
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16);
-  const int N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
-  const int Cout = w_prep.size(0);
-  TORCH_CHECK(conv3x3_supported(Cin));
-  const int Ho = 2 * H, Wo = 2 * W;
-  auto y = torch::empty({N, Cout, Ho, Wo},
-                        x.options().memory_format(
-                            torch::MemoryFormat::ChannelsLast));
-  static torch::Tensor zero_page;
-  if (!zero_page.defined() || zero_page.device() != x.device())
-    zero_page = torch::zeros({64}, x.options());
-  const long M = (long)N * Ho * Wo;
-  const long mtiles = (M + CONV_BM - 1) / CONV_BM;
-  dim3 grid((unsigned)((Cout + CONV_BN - 1) / CONV_BN),
-            (unsigned)std::min<long>(mtiles, 32768),
-            (unsigned)((mtiles + 32767) / 32768));
-  dim3 block(256);
-  const bool has_b = bias.has_value();
-  torch::Tensor bf32;
-  const float *bptr = nullptr;
-  if (has_b) {
-    bf32 = bias->to(torch::kFloat).contiguous();
-    bptr = bf32.data_ptr<float>();
-  }
-  float *gnp_ptr = nullptr;
-  if (gnp_out != nullptr && ((long)Ho * Wo) % 128 == 0) {
-    *gnp_out = torch::empty(
-        {M / 128, 2, (long)Cout}, x.options().dtype(torch::kFloat));
-    gnp_ptr = gnp_out->data_ptr<float>();
-  }
-  auto kern = has_b
-                  ? conv3x3_nhwc_bf16_kernel<true, false, false, 128, true>
-                  : conv3x3_nhwc_bf16_kernel<false, false, false, 128,
-                                             true>;
-  hipLaunchKernelGGL(kern, grid, block, 0, cur_stream(),
-                     (const __hip_bfloat16 *)x.data_ptr(),
-                     (const __hip_bfloat16 *)w_prep.data_ptr(), bptr,
-                     nullptr, nullptr,
-                     (const __hip_bfloat16 *)zero_page.data_ptr(),
-                     (__hip_bfloat16 *)y.data_ptr(), N, H, W, Cin, Cout,
-                     Ho, Wo, 1, Cout, gnp_ptr);
-  return y;
-}
-
-torch::Tensor ups2x_conv3x3(torch::Tensor x, torch::Tensor w_prep,
-                            c10::optional<torch::Tensor> bias) {
-  return ups2x_conv3x3_impl(x, w_prep, bias, nullptr);
-}
-
-std::vector<torch::Tensor> ups2x_conv3x3_gn(
-    torch::Tensor x, torch::Tensor w_prep,
-    c10::optional<torch::Tensor> bias) {
-  torch::Tensor gnp;
-  auto y = ups2x_conv3x3_impl(x, w_prep, bias, &gnp);
-  if (!gnp.defined()) gnp = torch::empty({0});
-  return {y, gnp};
+// nearest-2x upsample fused into the 3x3 conv (VAE decoder / UNet Upsample
+// blocks): output is [N, Cout, 2H, 2W]; returns (y, partials or None)
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> ups2x_conv3x3(
+    torch::Tensor x, torch::Tensor w_prep, c10::optional<torch::Tensor> bias,
+    bool collect_gn) {
+  ConvArgs a(x, w_prep, bias, c10::nullopt, c10::nullopt, 2 * x.size(2),
+             2 * x.size(3), collect_gn);
+  auto stream = cur_stream();
+  dispatch_bools(
+      [&](auto B) {
+        hipLaunchKernelGGL(
+            (conv3x3_nhwc_bf16_kernel<decltype(B)::value, false, false, 128,
+                                      true>),
+            conv_grid((a.Cout + CONV_BN - 1) / CONV_BN,
+                      (a.M + CONV_BM - 1) / CONV_BM),
+            dim3(256), 0, stream, a.x, a.w, a.bias, a.res, a.cb, a.zero,
+            a.yp, a.N, a.H, a.W, a.Cin, a.Cout, a.Ho, a.Wo, 1, a.Cout,
+            a.gnp_ptr);
+      },
+      a.bias != nullptr);
+  return a.result();
 }
 #endif
+

@@ -15,12 +15,9 @@ static inline hipStream_t cur_stream() {
 #include "softmax.hip"
 #include "probe.hip"
 #include "attention.hip"
-#include "conv_v3.hip"
 #include "conv_v4.hip"
 #include "conv.hip"
 #include "conv_small.hip"
-#include "gemm.hip"
-#include "gemm_v2.hip"
 
 #define CHECK_IN(x)                                                     \
   TORCH_CHECK(x.is_cuda(), #x " must be on GPU");                        \
@@ -370,8 +367,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("euler_step", &euler_step);
   m.def("group_norm_silu", &group_norm_silu);
   m.def("group_norm_silu_pre", &group_norm_silu_pre);
-  m.def("conv3x3_nhwc_gn", &conv3x3_nhwc_gn);
-  m.def("ups2x_conv3x3_gn", &ups2x_conv3x3_gn);
   m.def("layer_norm", &layer_norm);
   m.def("add_layer_norm", &add_layer_norm);
   m.def("row_softmax_", &row_softmax_);
@@ -383,11 +378,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_supported", &flash_supported);
   m.def("conv3x3_nhwc", &conv3x3_nhwc);
   m.def("conv3x3_supported", &conv3x3_supported);
+  m.def("conv3x3_plan", &conv3x3_plan);
   m.def("conv3x3_small", &conv3x3_small);
   m.def("ups2x_conv3x3", &ups2x_conv3x3);
   m.def("conv3x3_small_supported", &conv3x3_small_supported);
-  m.def("linear_bf16", &linear_bf16);
-  m.def("linear_supported", &linear_supported);
-  m.def("gemm_v2", &gemm_v2);
-  m.def("gemm_v2_supported", &gemm_v2_supported);
 }

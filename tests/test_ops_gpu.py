@@ -406,7 +406,7 @@ class TestConv3x3:
         y2 = ops.conv3x3(
             x2.contiguous(memory_format=torch.channels_last),
             c2.weight.permute(0, 2, 3, 1).contiguous(), c2.bias, res, 1,
-            collect_gn=True,
+            collect_gn=True, variant="v4",
         )
         assert hasattr(y2, "_sdwd_gnp")
         w2 = torch.randn(320, device=dev)
@@ -466,6 +466,127 @@ class TestConv3x3:
         wprep = conv.weight.permute(0, 2, 3, 1).contiguous()
         out = ops.conv3x3(xc, wprep, conv.bias, None, 1, chan_bias=cb)
         assert relerr(out.contiguous(), ref) < 0.05
+
+
+def _conv_case(dev, N, Cin, H, W, Cout, stride, extras=False, seed=11):
+    """Inputs for one conv (channels_last x, prepared weight, bias, optional
+    residual + chan_bias) and its fp32 F.conv2d reference."""
+    torch.manual_seed(seed)
+    x = torch.randn(N, Cin, H, W, device=dev, dtype=torch.bfloat16)
+    conv = torch.nn.Conv2d(Cin, Cout, 3, stride=stride, padding=1)
+    conv = conv.to(dev, torch.bfloat16)
+    ref = torch.nn.functional.conv2d(
+        x.float(), conv.weight.float(), conv.bias.float(),
+        stride=stride, padding=1,
+    )
+    res = cb = None
+    if extras:
+        res = torch.randn_like(ref, dtype=torch.bfloat16).contiguous(
+            memory_format=torch.channels_last
+        )
+        cb = torch.randn(N, Cout, device=dev, dtype=torch.bfloat16)
+        ref = ref + res.float() + cb.float()[:, :, None, None]
+    xc = x.contiguous(memory_format=torch.channels_last)
+    wprep = conv.weight.permute(0, 2, 3, 1).contiguous()
+    return xc, wprep, conv.bias, res, cb, ref
+
+
+class TestConv3x3Variants:
+    """The 256x256 v4 kernel forced at the smallest shapes that reach its
+    edges (the default dispatch only picks it on grids of >= 256 tiles)."""
+
+    def test_dispatch_table(self):
+        # conv3x3_plan(N, H, W, Cin, Cout, stride, force) -> (full 256-col
+        # v4 tiles, remainder cols on v2, remainder uses BN=64); host only
+        plan = ops.ext().conv3x3_plan
+        table = [
+            # N, Cin, H, W, Cout, stride, force -> expected
+            ((128, 320, 64, 64, 320, 1, 0), (1, 64, True)),
+            ((128, 640, 32, 32, 640, 1, 0), (2, 128, False)),
+            ((128, 960, 32, 32, 640, 1, 0), (2, 128, False)),
+            ((16, 512, 64, 64, 512, 1, 0), (2, 0, None)),
+            ((128, 1280, 16, 16, 1280, 1, 0), (0, 1280, False)),
+            ((8, 320, 64, 64, 320, 1, 0), (0, 320, False)),
+            ((2, 320, 32, 32, 320, 1, 0), (0, 320, True)),
+            ((128, 320, 64, 64, 320, 1, 2), (0, 320, False)),
+            ((1, 64, 17, 17, 320, 1, 4), (1, 64, True)),
+        ]
+        for (N, Cin, H, W, Cout, stride, force), want in table:
+            got = tuple(plan(N, H, W, Cin, Cout, stride, force))
+            if want[2] is None:  # no remainder launch: the flag is moot
+                got, want = got[:2], want[:2]
+            assert got == want, (N, Cin, H, W, Cout, stride, force, got)
+
+    @pytest.mark.parametrize("N,Cin,H,W,Cout,stride,extras", [
+        # 2 M-tiles (2nd: 33 live rows); one 256-col tile + 64-col v2 tail
+        (1, 64, 17, 17, 320, 1, False),
+        # one partial M-tile of 64 rows; 2 K-chunks/plane, 2 column tiles
+        (1, 128, 16, 16, 512, 2, False),
+        # residual + chan_bias together
+        (2, 64, 16, 16, 256, 1, True),
+    ])
+    def test_v4_vs_conv2d(self, dev, N, Cin, H, W, Cout, stride, extras):
+        xc, wprep, bias, res, cb, ref = _conv_case(
+            dev, N, Cin, H, W, Cout, stride, extras
+        )
+        plan = ops.ext().conv3x3_plan(N, H, W, Cin, Cout, stride, 4)
+        assert plan[0] == Cout // 256, "v4 was not reachable at this shape"
+        outs = {}
+        for variant in ("v4", "v2"):
+            out = ops.conv3x3(
+                xc, wprep, bias, res, stride, chan_bias=cb, variant=variant
+            )
+            outs[variant] = out
+            err = relerr(out.contiguous(), ref)
+            print(f"conv {variant} {(N, Cin, H, W, Cout, stride)} "
+                  f"relerr {err:.3e}")
+            assert err < 0.05, f"conv {variant} err {err}"
+        print(f"v4 bit-equal to v2: {torch.equal(outs['v4'], outs['v2'])}")
+
+    @pytest.mark.parametrize("N,Cin,H,W,Cout", [
+        (2, 64, 16, 16, 256),   # 4 slots of 128 rows
+        (1, 64, 16, 8, 256),    # M=128: the tile's second half is empty
+    ])
+    def test_v4_gn_partials(self, dev, N, Cin, H, W, Cout):
+        xc, wprep, bias, _, _, _ = _conv_case(dev, N, Cin, H, W, Cout, 1)
+        y = ops.conv3x3(
+            xc, wprep, bias, None, 1, collect_gn=True, variant="v4"
+        )
+        assert hasattr(y, "_sdwd_gnp"), "partials not attached"
+        gnp = y._sdwd_gnp[0]
+        M = N * H * W
+        assert tuple(gnp.shape) == (M // 128, 2, Cout)
+        # sums over the STORED bf16 values of each slot's 128 rows
+        v = y.permute(0, 2, 3, 1).reshape(M // 128, 128, Cout).double()
+        s_ref, q_ref = v.sum(1), (v * v).sum(1)
+        s_err = (gnp[:, 0].double() - s_ref).abs()
+        q_err = (gnp[:, 1].double() - q_ref).abs()
+        print(f"gn partial worst sum err/bound "
+              f"{(s_err / (1e-4 * v.abs().sum(1))).max().item():.3e}, "
+              f"sumsq err/bound {(q_err / (1e-4 * q_ref)).max().item():.3e}")
+        assert (s_err <= 1e-4 * v.abs().sum(1)).all()
+        assert (q_err <= 1e-4 * q_ref).all()
+        w = torch.randn(Cout, device=dev)
+        b = torch.randn(Cout, device=dev)
+        fused = ops.group_norm_silu(y, w, b, 32, 1e-5, True)
+        ref = torch.nn.functional.silu(
+            torch.nn.functional.group_norm(
+                y.float(), 32, w.float(), b.float()
+            )
+        )
+        assert relerr(fused.contiguous(), ref) < 0.03
+
+    def test_unknown_variant_raises(self, dev):
+        xc, wprep, bias, _, _, _ = _conv_case(dev, 2, 64, 16, 16, 64, 1)
+        with pytest.raises(ValueError):
+            ops.conv3x3(xc, wprep, bias, None, 1, variant="bogus")
+
+    def test_explicit_v2_equals_auto(self, dev):
+        # a shape where the automatic dispatch is the v2 kernel
+        xc, wprep, bias, _, _, _ = _conv_case(dev, 2, 64, 16, 16, 64, 1)
+        auto = ops.conv3x3(xc, wprep, bias, None, 1, variant="auto")
+        v2 = ops.conv3x3(xc, wprep, bias, None, 1, variant="v2")
+        assert torch.equal(auto, v2)
 
 
 class TestAddLayerNorm:
