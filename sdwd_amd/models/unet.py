@@ -323,7 +323,8 @@ class SpatialTransformer(nn.Module):
             x = blk(x, context)
         x = self.proj_out(x)
         x = x.reshape(b, h, w, c).permute(0, 3, 1, 2)
-        return x + residual
+        # the add also emits the next ResBlock's GroupNorm partials
+        return ops.add_gn(x, residual)
 
 
 class Downsample(nn.Module):
@@ -332,7 +333,7 @@ class Downsample(nn.Module):
         self.conv = SDConv2d(ch, ch, 3, stride=2, padding=1)
 
     def forward(self, x):
-        return self.conv(x)
+        return self.conv(x, collect_gn=True)
 
 
 class Upsample(nn.Module):

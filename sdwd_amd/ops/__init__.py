@@ -102,15 +102,16 @@ def group_norm_silu(
         )
         if not nhwc_ok and not x.is_contiguous():
             x = x.contiguous()
-        meta = getattr(x, "_sdwd_gnp", None)
-        if (
-            meta is not None
-            and nhwc_ok
-            and meta[2] == x._version
-            and meta[0].shape[-1] == c
-        ):
-            # stats come from the producing conv's epilogue side-channel:
-            # the full-tensor stats read is skipped entirely
+        if nhwc_ok and _gn_tile_eligible(x):
+            # stats come from the producer's side-channel (conv epilogue,
+            # add_gn): the full-tensor stats read is skipped entirely. A
+            # tensor nobody produced partials for gets them here, once,
+            # and keeps them for its later consumers.
+            meta = _valid_gn_partials(x)
+            if meta is None:
+                gnp = ext().gn_tile_stats(x)
+                _attach_gn_partials(x, gnp)
+                meta = (gnp, (x.shape[2] * x.shape[3]) // 128)
             return ext().group_norm_silu_pre(
                 x, weight, bias, groups, eps, silu, meta[0], meta[1]
             )
@@ -262,18 +263,71 @@ def _attach_gn_partials(
         y._sdwd_gnp = (gnp, tpi, y._version)
 
 
+def _gn_tile_eligible(x: torch.Tensor) -> bool:
+    """Can x carry the per-tile GroupNorm partials? bf16 channels_last on
+    the GPU, C % 8 == 0, and every 128-row tile inside one image."""
+    return (
+        x.is_cuda
+        and x.dim() == 4
+        and x.dtype == torch.bfloat16
+        and x.shape[1] % 8 == 0
+        and x.numel() > 0
+        and (x.shape[2] * x.shape[3]) % 128 == 0
+        and x.is_contiguous(memory_format=torch.channels_last)
+    )
+
+
+def _valid_gn_partials(x: torch.Tensor):
+    """x's (partials, tiles per image, version) side channel, or None when
+    it has none or was mutated in place since they were taken."""
+    meta = getattr(x, "_sdwd_gnp", None)
+    if (
+        meta is not None
+        and meta[2] == x._version
+        and meta[0].shape[-1] == x.shape[1]
+    ):
+        return meta
+    return None
+
+
+def add_gn(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """a + b (bit-equal to the ATen add) that also emits the sum's per-tile
+    GroupNorm partials in the same pass, so the next GroupNorm skips its
+    stats read (the SpatialTransformer exit). Shapes that cannot carry
+    partials get a plain add."""
+    if (
+        _gn_tile_eligible(a)
+        and _gn_tile_eligible(b)
+        and a.shape == b.shape
+    ):
+        out, gnp = ext().add_gn(a, b)
+        _attach_gn_partials(out, gnp)
+        return out
+    return a + b
+
+
 def cat_channels_gn(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """Channel-concat that PRESERVES the conv-epilogue GroupNorm partials:
-    a cat along C concatenates the per-channel partial sums too, so the
-    UNet up-path's skip-concat keeps the stats side-channel alive."""
+    """Channel-concat that PRESERVES the GroupNorm partials: a cat along C
+    concatenates the per-channel partial sums too, so the UNet up-path's
+    skip-concat keeps the stats side-channel alive. When exactly one half
+    lacks partials they are computed for that half alone (and stay attached
+    to it)."""
     out = torch.cat([a, b], dim=1)
-    ma = getattr(a, "_sdwd_gnp", None)
-    mb = getattr(b, "_sdwd_gnp", None)
+    ma = _valid_gn_partials(a)
+    mb = _valid_gn_partials(b)
+    if (ma is None) != (mb is None):
+        miss = a if ma is None else b
+        if _gn_tile_eligible(miss):
+            gnp = ext().gn_tile_stats(miss)
+            _attach_gn_partials(miss, gnp)
+            meta = (gnp, (miss.shape[2] * miss.shape[3]) // 128)
+            if ma is None:
+                ma = meta
+            else:
+                mb = meta
     if (
         ma is not None
         and mb is not None
-        and ma[2] == a._version
-        and mb[2] == b._version
         and ma[1] == mb[1]
         and ma[0].shape[0] == mb[0].shape[0]
     ):

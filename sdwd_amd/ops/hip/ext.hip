@@ -106,80 +106,149 @@ torch::Tensor euler_step(torch::Tensor x, torch::Tensor denoised, double sigma,
 }
 
 // ---------------------------------------------------------------------------
-torch::Tensor group_norm_silu_nhwc(torch::Tensor x, torch::Tensor w,
-                                   torch::Tensor b, long groups, double eps,
-                                   bool silu_act) {
-  // x: NCHW sizes, channels_last memory (= NHWC rows of C)
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "nhwc GN: bf16 only");
+// fp32 copy of a norm weight/bias for the kernels that read it as 16 B
+// vectors (a view at an odd storage offset is re-materialised)
+static torch::Tensor f32_vec_aligned(const torch::Tensor &t) {
+  auto f = t.to(torch::kFloat).contiguous();
+  if (reinterpret_cast<uintptr_t>(f.data_ptr()) % 16 != 0) f = f.clone();
+  return f;
+}
+
+static void check_nhwc_bf16(const torch::Tensor &x, const char *what) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
+                  x.scalar_type() == torch::kBFloat16 &&
+                  x.is_contiguous(torch::MemoryFormat::ChannelsLast) &&
+                  x.size(1) % 8 == 0,
+              what, ": bf16 channels_last with C % 8 == 0 only");
+}
+
+// Launch the tile-layout statistics kernel over a (or a + b -> out when b is
+// given); returns the partials [N*ceil(HW/128)][2][C].
+static torch::Tensor launch_gn_tile_stats(const torch::Tensor &a,
+                                          const torch::Tensor *b,
+                                          torch::Tensor *out) {
+  const long N = a.size(0);
+  const int C = a.size(1);
+  const long HW = a.size(2) * (long)a.size(3);
+  const long tpi = (HW + 127) / 128;
+  const int VC = C / 8;
+  int CB = 1;  // widest column slab <= 64 that divides VC
+  for (int d = std::min(VC, 64); d >= 1; --d)
+    if (VC % d == 0) {
+      CB = d;
+      break;
+    }
+  auto partial = torch::empty({N * tpi, 2L, (long)C},
+                              a.options().dtype(torch::kFloat));
+  if (N * tpi == 0) return partial;
+  TORCH_CHECK(N * tpi < (1L << 31), "gn tile stats: too many tiles");
+  dim3 grid((unsigned)(N * tpi), (unsigned)(VC / CB));
+  if (b) {
+    hipLaunchKernelGGL(gn_tile_stats_bf16<true>, grid, dim3(256), 0,
+                       cur_stream(), (const __hip_bfloat16 *)a.data_ptr(),
+                       (const __hip_bfloat16 *)b->data_ptr(),
+                       (__hip_bfloat16 *)out->data_ptr(),
+                       partial.data_ptr<float>(), C, HW, (int)tpi, CB);
+  } else {
+    hipLaunchKernelGGL(gn_tile_stats_bf16<false>, grid, dim3(256), 0,
+                       cur_stream(), (const __hip_bfloat16 *)a.data_ptr(),
+                       (const __hip_bfloat16 *)nullptr,
+                       (__hip_bfloat16 *)nullptr, partial.data_ptr<float>(),
+                       C, HW, (int)tpi, CB);
+  }
+  return partial;
+}
+
+// Per-tile per-channel (sum, sumsq) of one channels_last bf16 tensor, in the
+// layout the conv epilogues emit.
+torch::Tensor gn_tile_stats(torch::Tensor x) {
+  check_nhwc_bf16(x, "gn_tile_stats");
+  return launch_gn_tile_stats(x, nullptr, nullptr);
+}
+
+// a + b (bit-equal to the ATen bf16 add) and the sum's GroupNorm partials in
+// one pass over memory.
+std::tuple<torch::Tensor, torch::Tensor> add_gn(torch::Tensor a,
+                                                torch::Tensor b) {
+  check_nhwc_bf16(a, "add_gn");
+  check_nhwc_bf16(b, "add_gn");
+  TORCH_CHECK(a.sizes() == b.sizes(), "add_gn: shape mismatch");
+  auto out = torch::empty_like(a);  // keeps channels_last strides
+  auto partial = launch_gn_tile_stats(a, &b, &out);
+  return {out, partial};
+}
+
+// GroupNorm(+SiLU) over channels_last x from per-tile partials
+// [N*tiles_per_image][2][C]: finalize the per-(n, g) statistics, then the
+// normalise sweep.
+static torch::Tensor gn_nhwc_apply(const torch::Tensor &x,
+                                   const torch::Tensor &w,
+                                   const torch::Tensor &b, long groups,
+                                   double eps, bool silu_act,
+                                   const torch::Tensor &partial,
+                                   long tiles_per_image) {
   const long N = x.size(0);
   const int C = x.size(1);
   const long HW = x.size(2) * (long)x.size(3);
   TORCH_CHECK(C % 8 == 0 && C <= 3072, "nhwc GN: C%8==0 and C<=3072");
-  auto wf = w.to(torch::kFloat).contiguous();
-  auto bf = b.to(torch::kFloat).contiguous();
+  TORCH_CHECK(groups > 0 && C % groups == 0, "nhwc GN: C % groups != 0");
+  auto wf = f32_vec_aligned(w);
+  auto bf = f32_vec_aligned(b);
+  TORCH_CHECK(wf.numel() == C && bf.numel() == C, "nhwc GN: w/b size");
   auto out = torch::empty_like(x);  // keeps channels_last strides
-  const int S = (int)std::min<long>(
-      std::max<long>(1, 2048 / std::max<long>(N, 1)), (HW + 255) / 256);
-  auto opts = torch::TensorOptions()
-                  .dtype(torch::kFloat)
-                  .device(x.device());
-  const int VC = C / 8;
-  const int RP = VC >= 256 ? 1 : std::max(1, 256 / VC);
-  auto partial = torch::empty({(long)N * S * RP, 2L * C}, opts);
-  auto stats = torch::empty({N * (long)groups, 2L}, opts);
+  if (x.numel() == 0) return out;
+  auto stats = torch::empty({N * (long)groups, 2L},
+                            x.options().dtype(torch::kFloat));
   auto stream = cur_stream();
-  hipLaunchKernelGGL(gn_nhwc_partial_bf16, dim3((unsigned)(N * S)), dim3(256),
-                     0, stream, (const __hip_bfloat16 *)x.data_ptr(),
-                     partial.data_ptr<float>(), C, HW, S, RP);
   hipLaunchKernelGGL(gn_nhwc_stats, dim3((unsigned)(N * groups)), dim3(WAVE),
                      0, stream, partial.data_ptr<float>(),
-                     stats.data_ptr<float>(), C, HW, (int)groups, S * RP,
-                     (float)eps);
-  const long total = N * HW * (C / 8);
-  auto kern =
-      silu_act ? gn_nhwc_norm_bf16<true> : gn_nhwc_norm_bf16<false>;
-  hipLaunchKernelGGL(kern, dim3(ew_grid(total)), dim3(256), 0, stream,
-                     (const __hip_bfloat16 *)x.data_ptr(),
-                     stats.data_ptr<float>(), wf.data_ptr<float>(),
-                     bf.data_ptr<float>(),
-                     (__hip_bfloat16 *)out.data_ptr(), C, HW, (int)groups, N);
+                     stats.data_ptr<float>(), C, HW, (int)groups,
+                     (int)tiles_per_image, (float)eps);
+  // enough blocks to fill 256 CUs several times over, but at least ~4 rows
+  // per thread so the per-thread parameter loads stay amortised
+  const int VC = C / 8;
+  const long RP = VC <= 256 ? 256 / VC : 1;
+  const long S = std::max<long>(
+      1, std::min<long>(4096 / N, (HW + RP * 4 - 1) / (RP * 4)));
+  dispatch_bools(
+      [&](auto SL, auto TWO) {
+        hipLaunchKernelGGL(
+            (gn_nhwc_norm_bf16<decltype(SL)::value,
+                               decltype(TWO)::value ? 2 : 1>),
+            dim3((unsigned)(N * S)), dim3(256), 0, stream,
+            (const __hip_bfloat16 *)x.data_ptr(), stats.data_ptr<float>(),
+            wf.data_ptr<float>(), bf.data_ptr<float>(),
+            (__hip_bfloat16 *)out.data_ptr(), C, HW, (int)groups, (int)S);
+      },
+      silu_act, VC > 256);
   return out;
+}
+
+torch::Tensor group_norm_silu_nhwc(torch::Tensor x, torch::Tensor w,
+                                   torch::Tensor b, long groups, double eps,
+                                   bool silu_act) {
+  // x: NCHW sizes, channels_last memory (= NHWC rows of C)
+  check_nhwc_bf16(x, "nhwc GN");
+  const long HW = x.size(2) * (long)x.size(3);
+  auto partial = launch_gn_tile_stats(x, nullptr, nullptr);
+  return gn_nhwc_apply(x, w, b, groups, eps, silu_act, partial,
+                       (HW + 127) / 128);
 }
 
 torch::Tensor group_norm_silu_pre(torch::Tensor x, torch::Tensor w,
                                   torch::Tensor b, long groups, double eps,
                                   bool silu_act, torch::Tensor gnp,
                                   long tiles_per_image) {
-  // GroupNorm with conv-epilogue-emitted partials: skips the full-tensor
-  // stats read (gnp layout [n*tpi][2][C] == the stats kernel's [n][S][2][C])
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(x.is_contiguous(torch::MemoryFormat::ChannelsLast));
+  // GroupNorm with partials that a producer already emitted (conv epilogue,
+  // add_gn, gn_tile_stats): skips the full-tensor stats read
+  check_nhwc_bf16(x, "group_norm_silu_pre");
   const long N = x.size(0);
   const int C = x.size(1);
-  const long HW = x.size(2) * (long)x.size(3);
-  TORCH_CHECK(gnp.scalar_type() == torch::kFloat && gnp.is_contiguous());
+  TORCH_CHECK(gnp.is_cuda() && gnp.scalar_type() == torch::kFloat &&
+              gnp.is_contiguous());
   TORCH_CHECK(gnp.numel() == N * tiles_per_image * 2 * C,
               "gn partials shape mismatch");
-  auto wf = w.to(torch::kFloat).contiguous();
-  auto bf = b.to(torch::kFloat).contiguous();
-  auto out = torch::empty_like(x);
-  auto opts = torch::TensorOptions().dtype(torch::kFloat).device(x.device());
-  auto stats = torch::empty({N * (long)groups, 2L}, opts);
-  auto stream = cur_stream();
-  hipLaunchKernelGGL(gn_nhwc_stats, dim3((unsigned)(N * groups)),
-                     dim3(WAVE), 0, stream, gnp.data_ptr<float>(),
-                     stats.data_ptr<float>(), C, HW, (int)groups,
-                     (int)tiles_per_image, (float)eps);
-  const long total = N * HW * (C / 8);
-  auto kern =
-      silu_act ? gn_nhwc_norm_bf16<true> : gn_nhwc_norm_bf16<false>;
-  hipLaunchKernelGGL(kern, dim3(ew_grid(total)), dim3(256), 0, stream,
-                     (const __hip_bfloat16 *)x.data_ptr(),
-                     stats.data_ptr<float>(), wf.data_ptr<float>(),
-                     bf.data_ptr<float>(),
-                     (__hip_bfloat16 *)out.data_ptr(), C, HW, (int)groups,
-                     N);
-  return out;
+  return gn_nhwc_apply(x, w, b, groups, eps, silu_act, gnp, tiles_per_image);
 }
 
 torch::Tensor group_norm_silu(torch::Tensor x, torch::Tensor w,
@@ -261,12 +330,21 @@ std::vector<torch::Tensor> add_layer_norm(torch::Tensor x, torch::Tensor r,
   TORCH_CHECK(xc.scalar_type() == torch::kBFloat16 && D % 8 == 0 &&
                   D <= 1536,
               "add_layer_norm: bf16, D%8==0, D<=1536");
-  auto wf = w.to(torch::kFloat).contiguous();
-  auto bf = b.to(torch::kFloat).contiguous();
+  TORCH_CHECK(xc.is_cuda() && rc.scalar_type() == torch::kBFloat16 &&
+                  rc.sizes() == xc.sizes(),
+              "add_layer_norm: x and r must match");
+  auto wf = f32_vec_aligned(w);
+  auto bf = f32_vec_aligned(b);
+  TORCH_CHECK(wf.numel() == D && bf.numel() == D, "add_layer_norm: w/b size");
   auto out_sum = torch::empty_like(xc);
   auto out_ln = torch::empty_like(xc);
+  if (R == 0) return {out_sum, out_ln};
   dim3 grid((unsigned)((R + 3) / 4)), block(256);
-  hipLaunchKernelGGL(add_layer_norm_bf16_kernel, grid, block, 0, cur_stream(),
+  // vec8 slices per lane: D <= 512 -> 1, <= 1024 -> 2, <= 1536 -> 3
+  auto kern = D <= 512    ? add_layer_norm_bf16_kernel<1>
+              : D <= 1024 ? add_layer_norm_bf16_kernel<2>
+                          : add_layer_norm_bf16_kernel<3>;
+  hipLaunchKernelGGL(kern, grid, block, 0, cur_stream(),
                      (const __hip_bfloat16 *)xc.data_ptr(),
                      (const __hip_bfloat16 *)rc.data_ptr(),
                      wf.data_ptr<float>(), bf.data_ptr<float>(),
@@ -367,6 +445,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("euler_step", &euler_step);
   m.def("group_norm_silu", &group_norm_silu);
   m.def("group_norm_silu_pre", &group_norm_silu_pre);
+  m.def("gn_tile_stats", &gn_tile_stats);
+  m.def("add_gn", &add_gn);
   m.def("layer_norm", &layer_norm);
   m.def("add_layer_norm", &add_layer_norm);
   m.def("row_softmax_", &row_softmax_);
