@@ -72,7 +72,16 @@ class SDConv2d(nn.Conv2d):
     * 3x3 pad-1 with Cin 3/4/9 (the stem/IO convs) on GPU -> the direct
       small-Cin kernel (ops/hip/conv_small.hip);
     * everything else (CPU, other shapes) -> F.conv2d (MIOpen / native).
+
+    `circular` (True, or a (wrap_h, wrap_w) pair) switches the padding of
+    the wrapped axes to wrap-around (seamless tiling). The two native 3x3
+    kernels and the fused upsample take it as an addressing mode, so a
+    tiled conv keeps the fused epilogue and the GroupNorm partials.
     """
+
+    # False sends circular convs on the GPU back to F.pad + the library
+    # conv (A/B timing and the end-to-end comparison test)
+    native_circular = True
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -91,9 +100,18 @@ class SDConv2d(nn.Conv2d):
             return prep
         return cache[2]
 
+    def _wrap_axes(self) -> tuple[bool, bool]:
+        """(wrap_h, wrap_w) from `circular`: True wraps both axes (what the
+        pipeline's tiling switch sets), a pair wraps each axis on its own."""
+        c = getattr(self, "circular", False)
+        if isinstance(c, (tuple, list)):
+            return bool(c[0]), bool(c[1])
+        return bool(c), bool(c)
+
     def forward_upsampled2x(self, x: torch.Tensor) -> torch.Tensor:
         """conv(nearest2x(x)) with the upsample folded into the conv's
         im2col addressing on the GPU path (no 4x intermediate)."""
+        wrap = self._wrap_axes()
         if (
             x.is_cuda
             and x.dtype == torch.bfloat16
@@ -102,13 +120,13 @@ class SDConv2d(nn.Conv2d):
             and self.stride == (1, 1)
             and self.groups == 1
             and self.in_channels % 64 == 0
-            and not getattr(self, "circular", False)
+            and (self.native_circular or not any(wrap))
         ):
             from .. import ops
 
             xc = x.contiguous(memory_format=torch.channels_last)
             return ops.ups2x_conv3x3(
-                xc, self._wprep(), self.bias, collect_gn=True
+                xc, self._wprep(), self.bias, collect_gn=True, wrap=wrap
             )
         x = torch.nn.functional.interpolate(
             x, scale_factor=2, mode="nearest"
@@ -127,21 +145,14 @@ class SDConv2d(nn.Conv2d):
         from .. import ops
 
         k = self.kernel_size
-        if getattr(self, "circular", False) and self.padding != (0, 0):
-            # seamless-tiling mode (sdwui "Tiling"): wrap-around padding;
-            # runs the library conv (the HIP kernel is zero-pad only)
-            ph, pw = self.padding
-            xp = F.pad(x, (pw, pw, ph, ph), mode="circular")
-            out = F.conv2d(
-                xp, self.weight, self.bias, self.stride, 0,
-                self.dilation, self.groups,
-            )
-            if chan_bias is not None:
-                out = out + chan_bias.to(out.dtype)[:, :, None, None]
-            if residual is not None:
-                out = out + residual
-            return out
-        if x.is_cuda and x.dtype == torch.bfloat16:
+        # seamless-tiling mode (sdwui "Tiling"): wrap-around padding, per axis
+        wrap = self._wrap_axes()
+        tiled = any(wrap) and self.padding != (0, 0)
+        if (
+            x.is_cuda
+            and x.dtype == torch.bfloat16
+            and (self.native_circular or not tiled)
+        ):
             if (
                 k == (3, 3)
                 and self.padding == (1, 1)
@@ -158,7 +169,7 @@ class SDConv2d(nn.Conv2d):
                     )
                 return ops.conv3x3(
                     xc, self._wprep(), self.bias, res, self.stride[0],
-                    chan_bias, collect_gn=collect_gn,
+                    chan_bias, collect_gn=collect_gn, wrap=wrap,
                 )
             if (
                 k == (3, 3)
@@ -176,9 +187,14 @@ class SDConv2d(nn.Conv2d):
                 # of MIOpen's fallback solvers
                 xc = x.contiguous(memory_format=torch.channels_last)
                 return ops.conv3x3_small(
-                    xc, self._wprep(), self.bias, self.stride[0]
+                    xc, self._wprep(), self.bias, self.stride[0], wrap=wrap
                 )
-            if k == (1, 1) and self.stride == (1, 1) and self.groups == 1:
+            if (
+                k == (1, 1)
+                and self.stride == (1, 1)
+                and self.groups == 1
+                and not tiled
+            ):
                 xc = x.contiguous(memory_format=torch.channels_last)
                 n, c, h, w = xc.shape
                 rows = xc.permute(0, 2, 3, 1).reshape(n * h * w, c)
@@ -192,10 +208,23 @@ class SDConv2d(nn.Conv2d):
                 if residual is not None:
                     out = out + residual
                 return out
-        out = F.conv2d(
-            x, self.weight, self.bias, self.stride, self.padding,
-            self.dilation, self.groups,
-        )
+        if tiled:
+            # CPU, non-bf16, shapes the kernels do not take, or
+            # native_circular off: materialise the wrapped border with a
+            # circular pad on the wrapped axes and let the library conv
+            # zero-pad the others
+            ph, pw = self.padding
+            cp_h, cp_w = (ph if wrap[0] else 0), (pw if wrap[1] else 0)
+            xp = F.pad(x, (cp_w, cp_w, cp_h, cp_h), mode="circular")
+            out = F.conv2d(
+                xp, self.weight, self.bias, self.stride,
+                (ph - cp_h, pw - cp_w), self.dilation, self.groups,
+            )
+        else:
+            out = F.conv2d(
+                x, self.weight, self.bias, self.stride, self.padding,
+                self.dilation, self.groups,
+            )
         if chan_bias is not None:
             out = out + chan_bias.to(out.dtype)[:, :, None, None]
         if residual is not None:

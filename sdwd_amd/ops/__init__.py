@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -368,6 +368,7 @@ def conv3x3(
     chan_bias: Optional[torch.Tensor] = None,
     collect_gn: bool = False,
     variant: Optional[str] = None,
+    wrap: Tuple[bool, bool] = (False, False),
 ) -> torch.Tensor:
     """NHWC implicit-GEMM 3x3 conv (pad 1); bias, an optional residual and
     an optional per-(sample, channel) bias (the ResBlock time-embedding
@@ -376,10 +377,12 @@ def conv3x3(
     variant picks the kernel: "auto" is the measured dispatch
     (ext().conv3x3_plan), "v2" the 128-tile kernel everywhere, "v4" the
     256x256 pipeline on every legal shape; None follows SDWD_CONV.
+    wrap = (height, width): the padding on that axis wraps around (seamless
+    tiling) instead of reading zeros; it composes with everything above.
     GPU-only entry."""
     y, gnp = ext().conv3x3_nhwc(
         x, w_prep, bias, residual, chan_bias, stride, collect_gn,
-        _conv_force(variant),
+        _conv_force(variant), bool(wrap[0]), bool(wrap[1]),
     )
     _attach_gn_partials(y, gnp)
     return y
@@ -390,10 +393,14 @@ def conv3x3_small(
     w_prep: torch.Tensor,
     bias: Optional[torch.Tensor],
     stride: int = 1,
+    wrap: Tuple[bool, bool] = (False, False),
 ) -> torch.Tensor:
     """Direct 3x3 conv for tiny Cin (3/4/9: the stem/IO convs) — keeps the
-    whole pipeline off MIOpen's fallback solvers. GPU-only entry."""
-    return ext().conv3x3_small(x, w_prep, bias, stride)
+    whole pipeline off MIOpen's fallback solvers. wrap = (height, width)
+    selects wrap-around padding per axis. GPU-only entry."""
+    return ext().conv3x3_small(
+        x, w_prep, bias, stride, bool(wrap[0]), bool(wrap[1])
+    )
 
 
 def conv3x3_small_supported(cin: int, cout: int) -> bool:
@@ -411,10 +418,14 @@ def ups2x_conv3x3(
     w_prep: torch.Tensor,
     bias: Optional[torch.Tensor],
     collect_gn: bool = False,
+    wrap: Tuple[bool, bool] = (False, False),
 ) -> torch.Tensor:
     """Nearest-2x upsample fused into a 3x3 conv (VAE decoder / UNet
-    Upsample): no 4x intermediate tensor. GPU-only entry."""
-    y, gnp = ext().ups2x_conv3x3(x, w_prep, bias, collect_gn)
+    Upsample): no 4x intermediate tensor. wrap = (height, width) wraps the
+    conv's padding around the upsampled image. GPU-only entry."""
+    y, gnp = ext().ups2x_conv3x3(
+        x, w_prep, bias, collect_gn, bool(wrap[0]), bool(wrap[1])
+    )
     _attach_gn_partials(y, gnp)
     return y
 

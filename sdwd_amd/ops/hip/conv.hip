@@ -19,6 +19,9 @@
 //    lane-linear) so the b128 fragment reads are bank-conflict-free;
 //  * padding rows ride a 64-B zero page (glds is wave-uniform, lanes with
 //    out-of-image taps just read zeros);
+//  * WRAP instantiations (seamless tiling) instead fold an out-of-image
+//    tap back onto the opposite border, per axis (wrap_h / wrap_w): only
+//    the DMA source address differs, an unwrapped axis keeps the zero page;
 //  * bias, per-(sample,channel) bias (time embedding) and the ResBlock
 //    residual add are fused into the epilogue.
 //
@@ -49,8 +52,11 @@ typedef __attribute__((ext_vector_type(4))) float f32x4c;
 // input dims, Ho/Wo the upsampled-output dims): tap (h,w) of the virtual
 // image reads X[h>>1][w>>1], fusing Upsample+conv into one kernel with no
 // 4x intermediate tensor.
+// WRAP: "may wrap" - the border taps of an axis whose wrap_h / wrap_w flag is
+// set read the opposite border instead of the zero page (on the virtual
+// 2H x 2W grid for UPS). WRAP=false compiles the flags away.
 template <bool HAS_BIAS, bool HAS_RES, bool HAS_CB, int BN = 128,
-          bool UPS = false>
+          bool UPS = false, bool WRAP = false>
 __launch_bounds__(256, 2) __global__ void conv3x3_nhwc_bf16_kernel(
     const __hip_bfloat16 *__restrict__ X,   // [N,H,W,Cin]
     const __hip_bfloat16 *__restrict__ Wt,  // [Cout,3,3,Cin]
@@ -60,7 +66,8 @@ __launch_bounds__(256, 2) __global__ void conv3x3_nhwc_bf16_kernel(
     const __hip_bfloat16 *__restrict__ Zero,// >=16B of zeros
     __hip_bfloat16 *__restrict__ Y,         // [N,Ho,Wo,ldY] (+col offset)
     int Nn, int H, int W, int Cin, int Cout, int Ho, int Wo, int stride,
-    int ldY, float *__restrict__ GNP = nullptr) {
+    int ldY, float *__restrict__ GNP = nullptr, int wrap_h = 0,
+    int wrap_w = 0) {
   // GNP != null: emit per-(M-tile, channel) partial (sum, sumsq) of the
   // STORED values into GNP[mtile][2][ldY] so GroupNorm's stats pass can
   // skip its full-tensor read (host enables only when Ho*Wo % BM == 0,
@@ -111,6 +118,10 @@ __launch_bounds__(256, 2) __global__ void conv3x3_nhwc_bf16_kernel(
 
   const int kc_per_plane = Cin / CONV_BK;
   const int NT = 9 * kc_per_plane;
+  // WRAP: what folding a tap back adds to its address (host checks int)
+  const int row_elems = W * Cin, img_elems = H * row_elems;
+  (void)row_elems;
+  (void)img_elems;
 
   // stage tile t into buffer b (8 glds: 4 A + 4 B)
   auto stage = [&](int t, int b) {
@@ -126,7 +137,39 @@ __launch_bounds__(256, 2) __global__ void conv3x3_nhwc_bf16_kernel(
       const int sc = cswz(row, schunk);
       bool av;
       const __hip_bfloat16 *asrc;
-      if constexpr (UPS) {
+      if constexpr (WRAP && UPS) {
+        // wrap on the virtual 2H x 2W grid, then >> 1. |dy|,|dx| <= 1, so
+        // one conditional add per side folds the tap back
+        int vh = hs[i] + dy, vw = ws[i] + dx;
+        if (wrap_h) {
+          vh += vh < 0 ? 2 * H : 0;
+          vh -= vh >= 2 * H ? 2 * H : 0;
+        }
+        if (wrap_w) {
+          vw += vw < 0 ? 2 * W : 0;
+          vw -= vw >= 2 * W ? 2 * W : 0;
+        }
+        // a wrapped axis is in range by now: only unwrapped axes can fail
+        av = vh >= 0 && vh < 2 * H && vw >= 0 && vw < 2 * W;
+        asrc = av ? (X +
+                     (((long)nimg[i] * H + (vh >> 1)) * W + (vw >> 1)) *
+                         Cin +
+                     (long)kc * CONV_BK + sc * 8)
+                  : Zero;
+      } else if constexpr (WRAP) {
+        // (nimg, hh, ww) with hh = hs + dy folded back by one conditional
+        // add per side (|dy| <= 1, a stride-2 tap never passes the dim; also
+        // right at dim == 1) is abase + poff plus a whole image height or
+        // width: form that delta instead of redoing the 64-bit multiplies
+        const int hh = hs[i] + dy, ww = ws[i] + dx;
+        int dlt = 0;
+        if (wrap_h) dlt += hh < 0 ? img_elems : (hh >= H ? -img_elems : 0);
+        if (wrap_w) dlt += ww < 0 ? row_elems : (ww >= W ? -row_elems : 0);
+        // the tap is valid iff every UNWRAPPED axis is in range
+        av = (wrap_h || (hh >= 0 && hh < H)) &&
+             (wrap_w || (ww >= 0 && ww < W));
+        asrc = av ? (X + abase[i] + poff + dlt + sc * 8) : Zero;
+      } else if constexpr (UPS) {
         const int vh = hs[i] + dy, vw = ws[i] + dx;  // virtual 2H x 2W
         av = vh >= 0 && vh < 2 * H && vw >= 0 && vw < 2 * W;
         asrc = av ? (X +
@@ -415,11 +458,16 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> conv3x3_nhwc(
     torch::Tensor x, torch::Tensor w_prep, c10::optional<torch::Tensor> bias,
     c10::optional<torch::Tensor> residual,
     c10::optional<torch::Tensor> chan_bias, long stride, bool collect_gn,
-    long force) {
+    long force, bool wrap_h = false, bool wrap_w = false) {
   const int Ho = (x.size(2) + 2 - 3) / stride + 1;
   const int Wo = (x.size(3) + 2 - 3) / stride + 1;
   ConvArgs a(x, w_prep, bias, residual, chan_bias, Ho, Wo, collect_gn);
   auto stream = cur_stream();
+  // wrap-around padding (seamless tiling) picks the "may wrap"
+  // instantiation of whichever kernel the plan names; the plan is the same
+  const bool wrap = wrap_h || wrap_w;
+  TORCH_CHECK(!wrap || (long)a.H * a.W * a.Cin < (1L << 31),
+              "conv3x3: wrapped image too large");
   // v4: the 256x256 8-phase deep pipeline serves full 256-column tiles;
   // the v2 128-tile kernel covers the Cout remainder (e.g. 320 = 256+64).
   const auto [nfull, rem, bn64] =
@@ -427,35 +475,38 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> conv3x3_nhwc(
   if (nfull > 0) {
     const int cols = (int)(nfull * 256);
     dispatch_bools(
-        [&, cols](auto B, auto R, auto C) {
+        [&, cols](auto B, auto R, auto C, auto WR) {
           hipLaunchKernelGGL(
               (conv3x3_v4_kernel<decltype(B)::value, decltype(R)::value,
-                                 decltype(C)::value>),
+                                 decltype(C)::value, decltype(WR)::value>),
               conv_grid(cols / 256, (a.M + V4_BM - 1) / V4_BM), dim3(512), 0,
               stream, a.x, a.w, a.bias, a.res, a.cb, a.zero, a.yp, a.N, a.H,
-              a.W, a.Cin, cols, a.Cout, a.Ho, a.Wo, (int)stride, a.gnp_ptr);
+              a.W, a.Cin, cols, a.Cout, a.Ho, a.Wo, (int)stride, a.gnp_ptr,
+              (int)wrap_h, (int)wrap_w);
         },
-        a.bias != nullptr, a.res != nullptr, a.cb != nullptr);
+        a.bias != nullptr, a.res != nullptr, a.cb != nullptr, wrap);
   }
   if (rem > 0) {
     const long co0 = nfull * 256;
     const int cols = (int)rem;
     dispatch_bools(
-        [&, co0, cols](auto B, auto R, auto C, auto N64) {
+        [&, co0, cols](auto B, auto R, auto C, auto N64, auto WR) {
           constexpr int BN = decltype(N64)::value ? 64 : 128;
           hipLaunchKernelGGL(
               (conv3x3_nhwc_bf16_kernel<decltype(B)::value,
                                         decltype(R)::value,
-                                        decltype(C)::value, BN>),
+                                        decltype(C)::value, BN, false,
+                                        decltype(WR)::value>),
               conv_grid((cols + BN - 1) / BN,
                         (a.M + CONV_BM - 1) / CONV_BM),
               dim3(256), 0, stream, a.x, a.w + co0 * 9 * a.Cin,
               a.bias ? a.bias + co0 : nullptr, a.res ? a.res + co0 : nullptr,
               a.cb ? a.cb + co0 : nullptr, a.zero, a.yp + co0, a.N, a.H, a.W,
               a.Cin, cols, a.Ho, a.Wo, (int)stride, a.Cout,
-              a.gnp_ptr ? a.gnp_ptr + co0 : nullptr);
+              a.gnp_ptr ? a.gnp_ptr + co0 : nullptr, (int)wrap_h,
+              (int)wrap_w);
         },
-        a.bias != nullptr, a.res != nullptr, a.cb != nullptr, bn64);
+        a.bias != nullptr, a.res != nullptr, a.cb != nullptr, bn64, wrap);
   }
   return a.result();
 }
@@ -464,22 +515,22 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> conv3x3_nhwc(
 // blocks): output is [N, Cout, 2H, 2W]; returns (y, partials or None)
 std::tuple<torch::Tensor, c10::optional<torch::Tensor>> ups2x_conv3x3(
     torch::Tensor x, torch::Tensor w_prep, c10::optional<torch::Tensor> bias,
-    bool collect_gn) {
+    bool collect_gn, bool wrap_h = false, bool wrap_w = false) {
   ConvArgs a(x, w_prep, bias, c10::nullopt, c10::nullopt, 2 * x.size(2),
              2 * x.size(3), collect_gn);
   auto stream = cur_stream();
   dispatch_bools(
-      [&](auto B) {
+      [&](auto B, auto WR) {
         hipLaunchKernelGGL(
             (conv3x3_nhwc_bf16_kernel<decltype(B)::value, false, false, 128,
-                                      true>),
+                                      true, decltype(WR)::value>),
             conv_grid((a.Cout + CONV_BN - 1) / CONV_BN,
                       (a.M + CONV_BM - 1) / CONV_BM),
             dim3(256), 0, stream, a.x, a.w, a.bias, a.res, a.cb, a.zero,
             a.yp, a.N, a.H, a.W, a.Cin, a.Cout, a.Ho, a.Wo, 1, a.Cout,
-            a.gnp_ptr);
+            a.gnp_ptr, (int)wrap_h, (int)wrap_w);
       },
-      a.bias != nullptr);
+      a.bias != nullptr, wrap_h || wrap_w);
   return a.result();
 }
 #endif

@@ -11,13 +11,16 @@
 // held in registers.
 #include "common.h"
 
-template <bool HAS_BIAS, int CIN>
+// WRAP: "may wrap" (seamless tiling) - the border taps of an axis whose
+// wrap_h / wrap_w flag is set read the opposite border instead of zeros.
+template <bool HAS_BIAS, int CIN, bool WRAP = false>
 __launch_bounds__(256, 4) __global__ void conv3x3_smallcin_kernel(
     const __hip_bfloat16 *__restrict__ X,   // [N,H,W,Cin] channels_last
     const __hip_bfloat16 *__restrict__ Wt,  // [Cout,3,3,Cin]
     const float *__restrict__ bias,         // [Cout] or null
     __hip_bfloat16 *__restrict__ Y,         // [N,Ho,Wo,Cout]
-    int Nn, int H, int W, int Cout, int Ho, int Wo, int stride) {
+    int Nn, int H, int W, int Cout, int Ho, int Wo, int stride,
+    int wrap_h = 0, int wrap_w = 0) {
   constexpr int TAPS = 9 * CIN;
   constexpr int PIX = 64;                  // pixels per block
   extern __shared__ __align__(16) __bf16 wl[];  // [TAPS][Cout]
@@ -48,7 +51,18 @@ __launch_bounds__(256, 4) __global__ void conv3x3_smallcin_kernel(
 #pragma unroll
   for (int t = 0; t < 9; ++t) {
     const int dy = t / 3 - 1, dx = t % 3 - 1;
-    const int h = hi + dy, w = wi + dx;
+    int h = hi + dy, w = wi + dx;
+    if constexpr (WRAP) {
+      // one conditional add per side is enough (|dy|,|dx| <= 1)
+      if (wrap_h) {
+        h += h < 0 ? H : 0;
+        h -= h >= H ? H : 0;
+      }
+      if (wrap_w) {
+        w += w < 0 ? W : 0;
+        w -= w >= W ? W : 0;
+      }
+    }
     const bool ok = h >= 0 && h < H && w >= 0 && w < W;
     const __hip_bfloat16 *src =
         X + (((long)n_img * H + h) * W + w) * CIN;
@@ -95,7 +109,8 @@ bool conv3x3_small_supported(long cin, long cout) {
 
 torch::Tensor conv3x3_small(torch::Tensor x, torch::Tensor w_prep,
                             c10::optional<torch::Tensor> bias,
-                            long stride) {
+                            long stride, bool wrap_h = false,
+                            bool wrap_w = false) {
   TORCH_CHECK(x.is_contiguous(torch::MemoryFormat::ChannelsLast),
               "conv3x3_small: x must be channels_last");
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16);
@@ -118,20 +133,24 @@ torch::Tensor conv3x3_small(torch::Tensor x, torch::Tensor w_prep,
   dim3 grid((unsigned)((M + 63) / 64)), block(256);
   const size_t lds = (size_t)9 * Cin * Cout * 2;
   auto stream = cur_stream();
-#define LAUNCH_SC(CIN_, HB_)                                                \
-  hipLaunchKernelGGL((conv3x3_smallcin_kernel<HB_, CIN_>), grid, block,     \
-                     lds, stream, (const __hip_bfloat16 *)x.data_ptr(),     \
-                     (const __hip_bfloat16 *)w_prep.data_ptr(), bptr,       \
-                     (__hip_bfloat16 *)y.data_ptr(), N, H, W, Cout, Ho,     \
-                     Wo, (int)stride)
-  if (Cin == 3) {
-    if (has_b) LAUNCH_SC(3, true); else LAUNCH_SC(3, false);
-  } else if (Cin == 4) {
-    if (has_b) LAUNCH_SC(4, true); else LAUNCH_SC(4, false);
-  } else {
-    if (has_b) LAUNCH_SC(9, true); else LAUNCH_SC(9, false);
-  }
-#undef LAUNCH_SC
+  dispatch_bools(
+      [&](auto HB, auto WR) {
+        auto launch = [&](auto kern) {
+          hipLaunchKernelGGL(kern, grid, block, lds, stream,
+                             (const __hip_bfloat16 *)x.data_ptr(),
+                             (const __hip_bfloat16 *)w_prep.data_ptr(), bptr,
+                             (__hip_bfloat16 *)y.data_ptr(), N, H, W, Cout,
+                             Ho, Wo, (int)stride, (int)wrap_h, (int)wrap_w);
+        };
+        constexpr bool hb = decltype(HB)::value, wr = decltype(WR)::value;
+        if (Cin == 3)
+          launch(conv3x3_smallcin_kernel<hb, 3, wr>);
+        else if (Cin == 4)
+          launch(conv3x3_smallcin_kernel<hb, 4, wr>);
+        else
+          launch(conv3x3_smallcin_kernel<hb, 9, wr>);
+      },
+      has_b, wrap_h || wrap_w);
   return y;
 }
 #endif

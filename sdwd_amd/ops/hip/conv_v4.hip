@@ -30,7 +30,8 @@ __device__ __forceinline__ int cswz(int row, int chunk) {
 #define V4_BK 64
 #define V4_ATILE (V4_BM * V4_BK)  // elements per A buffer
 
-template <bool HAS_BIAS, bool HAS_RES, bool HAS_CB>
+// WRAP: "may wrap" (seamless tiling) - see conv.hip.
+template <bool HAS_BIAS, bool HAS_RES, bool HAS_CB, bool WRAP = false>
 __launch_bounds__(512, 2) __global__ void conv3x3_v4_kernel(
     const __hip_bfloat16 *__restrict__ X,   // [N,H,W,Cin]
     const __hip_bfloat16 *__restrict__ Wt,  // [Cout,3,3,Cin] (+col offset)
@@ -40,7 +41,8 @@ __launch_bounds__(512, 2) __global__ void conv3x3_v4_kernel(
     const __hip_bfloat16 *__restrict__ Zero,
     __hip_bfloat16 *__restrict__ Y,         // [M,ldY] (+col offset)
     int Nn, int H, int W, int Cin, int Cols, int ldY, int Ho, int Wo,
-    int stride, float *__restrict__ GNP = nullptr) {
+    int stride, float *__restrict__ GNP = nullptr, int wrap_h = 0,
+    int wrap_w = 0) {
   // GNP: per-(M-tile, channel) partial (sum, sumsq) of the stored values
   // (see conv.hip - lets GroupNorm skip its full-tensor stats read).
   __shared__ __align__(16) __bf16 smem[4 * V4_ATILE];  // [buf][A|B]
@@ -78,6 +80,10 @@ __launch_bounds__(512, 2) __global__ void conv3x3_v4_kernel(
 
   const int kc_per_plane = Cin / V4_BK;
   const int NT = 9 * kc_per_plane;
+  // WRAP: what folding a tap back adds to its address (host checks int)
+  const int row_elems = W * Cin, img_elems = H * row_elems;
+  (void)row_elems;
+  (void)img_elems;
 
   // stage ALL 8 pieces of tile t into buffer b at once. Issued at phase 0
   // of the previous tile (that buffer's readers finished a barrier-pair
@@ -102,10 +108,24 @@ __launch_bounds__(512, 2) __global__ void conv3x3_v4_kernel(
       if (i < 4) {
         const int row = prow + 64 * i;
         const int swz = cswz(row, sc);
-        const bool av = (hs[i] + dy >= 0) && (hs[i] + dy < H) &&
-                        (ws[i] + dx >= 0) && (ws[i] + dx < W);
-        const __hip_bfloat16 *asrc =
-            av ? (X + abase[i] + poff + swz * 8) : Zero;
+        bool av;
+        const __hip_bfloat16 *asrc;
+        if constexpr (WRAP) {
+          // the folded-back tap is abase + poff plus a whole image height
+          // or width (see conv.hip): no extra per-row state, no multiplies
+          const int hh = hs[i] + dy, ww = ws[i] + dx;
+          int dlt = 0;
+          if (wrap_h) dlt += hh < 0 ? img_elems : (hh >= H ? -img_elems : 0);
+          if (wrap_w) dlt += ww < 0 ? row_elems : (ww >= W ? -row_elems : 0);
+          // the tap is valid iff every UNWRAPPED axis is in range
+          av = (wrap_h || (hh >= 0 && hh < H)) &&
+               (wrap_w || (ww >= 0 && ww < W));
+          asrc = av ? (X + abase[i] + poff + dlt + swz * 8) : Zero;
+        } else {
+          av = (hs[i] + dy >= 0) && (hs[i] + dy < H) &&
+               (ws[i] + dx >= 0) && (ws[i] + dx < W);
+          asrc = av ? (X + abase[i] + poff + swz * 8) : Zero;
+        }
         __builtin_amdgcn_global_load_lds(
             (const __attribute__((address_space(1))) unsigned int *)asrc,
             (__attribute__((address_space(3))) unsigned int

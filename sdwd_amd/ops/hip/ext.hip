@@ -456,10 +456,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("probe_mfma16", &probe_mfma16);
   m.def("probe_tr16", &probe_tr16);
   m.def("flash_supported", &flash_supported);
-  m.def("conv3x3_nhwc", &conv3x3_nhwc);
+  // the wrap flags (seamless tiling) go last, defaulted: earlier callers
+  // pass everything before them positionally
+  m.def("conv3x3_nhwc", &conv3x3_nhwc, py::arg("x"), py::arg("w_prep"),
+        py::arg("bias"), py::arg("residual"), py::arg("chan_bias"),
+        py::arg("stride"), py::arg("collect_gn"), py::arg("force"),
+        py::arg("wrap_h") = false, py::arg("wrap_w") = false);
   m.def("conv3x3_supported", &conv3x3_supported);
   m.def("conv3x3_plan", &conv3x3_plan);
-  m.def("conv3x3_small", &conv3x3_small);
-  m.def("ups2x_conv3x3", &ups2x_conv3x3);
+  m.def("conv3x3_small", &conv3x3_small, py::arg("x"), py::arg("w_prep"),
+        py::arg("bias"), py::arg("stride"), py::arg("wrap_h") = false,
+        py::arg("wrap_w") = false);
+  m.def("ups2x_conv3x3", &ups2x_conv3x3, py::arg("x"), py::arg("w_prep"),
+        py::arg("bias"), py::arg("collect_gn"), py::arg("wrap_h") = false,
+        py::arg("wrap_w") = false);
   m.def("conv3x3_small_supported", &conv3x3_small_supported);
 }

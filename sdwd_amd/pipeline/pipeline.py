@@ -610,7 +610,9 @@ class StableDiffusionPipeline:
             ):
                 if isinstance(m, SDConv2d):
                     m.circular = req.tiling
-            # captured graphs baked the old padding path
+            # the native conv kernels take the wrap as an addressing mode
+            # (same kernels, fused epilogues and GroupNorm partials as the
+            # zero-pad run); captured graphs baked the old padding mode
             self._denoiser.cache.clear()
             self._wholestep_cache.clear()
             self._tiling = req.tiling

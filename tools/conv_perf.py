@@ -1,5 +1,11 @@
 #!/usr/bin/env python3
-"""Our conv3x3 vs MIOpen F.conv2d on the SD hot shapes (channels_last)."""
+"""Our conv3x3 vs MIOpen F.conv2d on the SD hot shapes (channels_last).
+
+--wrap adds, per shape, the wrapped (seamless-tiling) native time next to
+the plain native time, and the time of the library route a tiled conv took
+before the kernels could wrap: F.pad(mode="circular") + F.conv2d.
+"""
+import argparse
 import json
 import os
 import sys
@@ -27,6 +33,12 @@ SHAPES = [
 ]
 
 
+ap = argparse.ArgumentParser(description=__doc__)
+ap.add_argument("--wrap", action="store_true",
+                help="also time wrap=(True, True) and F.pad(circular)+conv2d")
+args = ap.parse_args()
+
+
 def t(fn, warm=2, it=6):
     for _ in range(warm):
         fn()
@@ -39,7 +51,7 @@ def t(fn, warm=2, it=6):
 
 
 out = {}
-tot_ours = tot_miopen = 0.0
+tot_ours = tot_miopen = tot_wrap = tot_padlib = 0.0
 for (N, Ci, H, W, Co, s) in SHAPES:
     x = torch.randn(N, Ci, H, W, device="cuda", dtype=torch.bfloat16)
     xc = x.contiguous(memory_format=torch.channels_last)
@@ -59,6 +71,23 @@ for (N, Ci, H, W, Co, s) in SHAPES:
     }
     tot_ours += t_ours
     tot_miopen += t_mi
+    if args.wrap:
+        t_wrap = t(lambda: ops.conv3x3(xc, wp, b, None, s,
+                                       wrap=(True, True)))
+        t_pad = t(lambda: F.conv2d(F.pad(xc, (1, 1, 1, 1), mode="circular"),
+                                   wcl, b, stride=s))
+        out[key].update({
+            "wrap_ms": round(t_wrap * 1e3, 3),
+            "wrap_tf": round(flops / t_wrap / 1e12, 1),
+            "wrap_vs_plain": round(t_wrap / t_ours, 3),
+            "padlib_ms": round(t_pad * 1e3, 3),
+            "padlib_tf": round(flops / t_pad / 1e12, 1),
+        })
+        tot_wrap += t_wrap
+        tot_padlib += t_pad
 out["_total"] = {"ours_ms": round(tot_ours * 1e3, 2),
                  "miopen_ms": round(tot_miopen * 1e3, 2)}
+if args.wrap:
+    out["_total"].update({"wrap_ms": round(tot_wrap * 1e3, 2),
+                          "padlib_ms": round(tot_padlib * 1e3, 2)})
 print(json.dumps(out, indent=1))
