@@ -152,22 +152,61 @@ def add_layer_norm(x, res, weight, bias, eps: float = 1e-5):
 # ---------------------------------------------------------------------------
 # attention (flash-style, fused softmax(QK^T/sqrt(d))·V)
 # ---------------------------------------------------------------------------
+# flash kernel variants -> the extension's `force` argument; SDWD_ATTN keeps
+# its historical spellings (v2, v3all)
+_ATTN_FORCE = {"auto": 0, "v2": 2, "v3": 3}
+_ATTN_ENV = {"v2": 2, "v3all": 3}
+_ATTN_ENV_FORCE: Optional[int] = None
+
+
+def _attn_force(variant: Optional[str]) -> int:
+    """None -> SDWD_ATTN (read once; v2 / v3all, anything else is auto); an
+    explicit variant always wins and must be one of auto/v2/v3."""
+    global _ATTN_ENV_FORCE
+    if variant is None:
+        if _ATTN_ENV_FORCE is None:
+            _ATTN_ENV_FORCE = _ATTN_ENV.get(
+                os.environ.get("SDWD_ATTN", ""), 0
+            )
+        return _ATTN_ENV_FORCE
+    if variant not in _ATTN_FORCE:
+        raise ValueError(
+            f"attention: unknown variant {variant!r} "
+            f"(expected one of {sorted(_ATTN_FORCE)})"
+        )
+    return _ATTN_FORCE[variant]
+
+
 def attention(
     q: torch.Tensor,
     k: torch.Tensor,
     v: torch.Tensor,
     scale: Optional[float] = None,
+    variant: Optional[str] = None,
 ) -> torch.Tensor:
     """q,k,v: [B, H, S, D] -> [B, H, Sq, D]. bf16 in/out on GPU, fp32 accum.
 
     GPU path: hand-written MFMA flash-forward kernel (ops/hip/attention.hip),
-    online softmax, D padded to a multiple of 16 in-kernel.
+    online softmax, D padded to a multiple of 16 in-kernel. variant picks
+    the kernel: "auto" is the measured dispatch (ext().attention_plan), "v2"
+    / "v3" force one flash kernel and raise on a head dim that has none;
+    None follows SDWD_ATTN.
     CPU path: explicit fp32 reference (the numerics oracle).
     """
+    force = _attn_force(variant)
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     if q.is_cuda:
-        return ext().attention_fwd(q, k, v, scale)
+        # SDWD_ATTN only steers calls that a flash kernel can take (an A/B
+        # run still composes the VAE's D=512); an explicit variant on any
+        # other call is an error in the extension
+        if variant is None and not (
+            ext().flash_supported(q.shape[-1])
+            and q.dtype == torch.bfloat16
+            and q.stride(-1) == k.stride(-1) == v.stride(-1) == 1
+        ):
+            force = 0
+        return ext().attention_fwd(q, k, v, scale, force)
     qf, kf, vf = q.float(), k.float(), v.float()
     s = torch.matmul(qf, kf.transpose(-1, -2)) * scale
     p = torch.softmax(s, dim=-1)
@@ -179,22 +218,25 @@ def attention_bshd(
     k: torch.Tensor,
     v: torch.Tensor,
     scale: Optional[float] = None,
+    variant: Optional[str] = None,
 ) -> torch.Tensor:
     """q,k,v: [B, S, H, D] (natural projection layout) -> [B, Sq, H, D].
 
     GPU: strided flash kernel, zero transpose/pad copies. CPU (or an
-    unsupported head dim): permuted reference path.
+    unsupported head dim): permuted reference path. variant as in
+    attention().
     """
+    force = _attn_force(variant)
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     if q.is_cuda:
         mod = ext()
         d = q.shape[-1]
         if mod.flash_supported(d):
-            return mod.attention_fwd_bshd(q, k, v, scale)
+            return mod.attention_fwd_bshd(q, k, v, scale, force)
     out = attention(
         q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3),
-        scale,
+        scale, variant,
     )
     return out.permute(0, 2, 1, 3)
 

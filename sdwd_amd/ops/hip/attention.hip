@@ -576,11 +576,37 @@ bool flash_supported(long d_head) {
 #ifdef __HIP_PLATFORM_AMD__
 static inline long round16(long d) { return (d + 15) / 16 * 16; }
 
+// Which kernel serves an attention call: {"v2" | "v3" | "composed", padded
+// head dim, q rows per workgroup}. "composed" is the GEMM + row_softmax_
+// path of attention_fwd (head dims the flash kernels do not take); its
+// other two fields are 0. force: 0 = measured policy, 2 = v2, 3 = v3 (A/B
+// tooling and tests); a forced flash kernel on an unsupported head dim is
+// an error, never a silent composition. The launcher below follows this
+// and nothing else decides.
+std::tuple<std::string, long, long> attention_plan(long d_head, long sk,
+                                                   long force) {
+  TORCH_CHECK(force == 0 || force == 2 || force == 3,
+              "attention: force must be 0 (auto), 2 (v2) or 3 (v3)");
+  if (!flash_supported(d_head)) {
+    TORCH_CHECK(force == 0, "attention: head dim ", d_head,
+                " has no flash kernel; variant v", force,
+                " cannot be forced");
+    return {"composed", 0, 0};
+  }
+  const long dpad = round16(d_head);
+  // measured dispatch: v3 wins every self-attention shape (at D>64 its
+  // prologue/epilogue spills are off the hot loop: +24% at D=80, +7% at
+  // D=160); the short-Sk cross shapes (Sk=77) stay on v2
+  const bool v2 = force == 2 || (force == 0 && dpad > 64 && sk < 256);
+  if (v2) return {"v2", dpad, 256};
+  return {"v3", dpad, dpad <= 96 ? 256 : 128};  // QS * 128
+}
+
 // qkv layout: "bhsd" (q.size = [B,H,S,D]) or "bshd" ([B,S,H,D]); tensors
 // need unit stride in D and 16-byte-aligned row starts, NOT full contiguity.
 static torch::Tensor flash_attention_raw(torch::Tensor q, torch::Tensor k,
                                          torch::Tensor v, double scale,
-                                         bool bshd) {
+                                         bool bshd, long force) {
   const long B = q.size(0);
   const long H = bshd ? q.size(2) : q.size(1);
   const long Sq = bshd ? q.size(1) : q.size(2);
@@ -605,22 +631,16 @@ static torch::Tensor flash_attention_raw(torch::Tensor q, torch::Tensor k,
   const long DP = round16(D);
   dim3 block(256);
   auto stream = cur_stream();
-  static const bool use_v2 = [] {
-    const char *e = getenv("SDWD_ATTN");
-    return e && strcmp(e, "v2") == 0;
-  }();
-  static const bool v3all = [] {  // measure v3 past DPAD 64 (spilly)
-    const char *e = getenv("SDWD_ATTN");
-    return e && strcmp(e, "v3all") == 0;
-  }();
+  // the plan decides v2 vs v3 and the block's q-row extent; nothing else
+  const auto [kernel, dpad_, qrows] = attention_plan(D, Sk, force);
+  TORCH_CHECK(dpad_ == DP, "flash: plan/launch padded head dim mismatch");
+  const bool run_v2 = kernel == "v2";
+
+  const dim3 grid((unsigned)((Sq + qrows - 1) / qrows), (unsigned)(B * H));
 
 #define LAUNCH_FLASH(DP_)                                                   \
   do {                                                                      \
-    /* measured dispatch: v3 wins every self-attention shape (at D>64     \
-       its prologue/epilogue spills are off the hot loop: +24% at D=80,  \
-       +7% at D=160); the short-Sk cross shapes (Sk=77) stay on v2 */    \
-    if (use_v2 || (DP_ > 64 && !v3all && Sk < 256)) {                    \
-      dim3 grid((unsigned)((Sq + 255) / 256), (unsigned)(B * H));           \
+    if (run_v2) {                                                           \
       hipLaunchKernelGGL(flash_fwd_bf16_kernel<DP_>, grid, block, 0,        \
                          stream, (const __hip_bfloat16 *)q.data_ptr(),      \
                          (const __hip_bfloat16 *)k.data_ptr(),              \
@@ -628,8 +648,8 @@ static torch::Tensor flash_attention_raw(torch::Tensor q, torch::Tensor k,
                          (__hip_bfloat16 *)out.data_ptr(), (int)H, Sq, Sk,  \
                          (int)D, (float)scale, st);                         \
     } else {                                                                \
-      constexpr long ROWS_ = (DP_ <= 96 ? 256 : 128); /* QS*128 */          \
-      dim3 grid((unsigned)((Sq + ROWS_ - 1) / ROWS_), (unsigned)(B * H));   \
+      TORCH_CHECK(qrows == (DP_ <= 96 ? 256 : 128),                         \
+                  "flash: plan rows do not match the v3 instantiation");    \
       hipLaunchKernelGGL(flash_fwd_bf16_v3<DP_>, grid, block, 0, stream,    \
                          (const __hip_bfloat16 *)q.data_ptr(),              \
                          (const __hip_bfloat16 *)k.data_ptr(),              \
@@ -657,8 +677,4 @@ static torch::Tensor flash_attention_raw(torch::Tensor q, torch::Tensor k,
   return out;
 }
 
-torch::Tensor flash_attention_bf16(torch::Tensor q, torch::Tensor k,
-                                   torch::Tensor v, double scale) {
-  return flash_attention_raw(q, k, v, scale, /*bshd=*/false);
-}
 #endif

@@ -373,12 +373,21 @@ void row_softmax_(torch::Tensor x, double scale) {
 }
 
 torch::Tensor attention_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                            double scale) {
-  // [B,H,S,D]; the flash path reads strided (no transpose/pad copies)
-  if (q.scalar_type() == torch::kBFloat16 && flash_supported(q.size(3)) &&
-      q.stride(3) == 1 && k.stride(3) == 1 && v.stride(3) == 1) {
-    return flash_attention_raw(q, k, v, scale, /*bshd=*/false);
+                            double scale, long force = 0) {
+  // [B,H,S,D]; the flash path reads strided (no transpose/pad copies).
+  // attention_plan names the kernel (and rejects a forced flash kernel on
+  // a head dim that has none); a flash plan also needs bf16, unit-stride D
+  const bool flash_layout = q.scalar_type() == torch::kBFloat16 &&
+                            q.stride(3) == 1 && k.stride(3) == 1 &&
+                            v.stride(3) == 1;
+  const bool composed =
+      std::get<0>(attention_plan(q.size(3), k.size(2), force)) == "composed";
+  if (!composed && flash_layout) {
+    return flash_attention_raw(q, k, v, scale, /*bshd=*/false, force);
   }
+  TORCH_CHECK(force == 0,
+              "attention_fwd: a forced flash kernel needs bf16 q/k/v with "
+              "unit stride in D");
   auto qc = q.contiguous(), kc = k.contiguous(), vc = v.contiguous();
   const long B = qc.size(0), H = qc.size(1);
   const long Sq = qc.size(2), Sk = kc.size(2), D = qc.size(3);
@@ -430,12 +439,13 @@ torch::Tensor probe_tr16(long stride_bytes, long base_bytes) {
 }
 
 torch::Tensor attention_fwd_bshd(torch::Tensor q, torch::Tensor k,
-                                 torch::Tensor v, double scale) {
+                                 torch::Tensor v, double scale,
+                                 long force = 0) {
   // [B,S,H,D] (the natural projection layout; avoids transposes entirely)
   TORCH_CHECK(q.scalar_type() == torch::kBFloat16 &&
                   flash_supported(q.size(3)),
               "attention_fwd_bshd: bf16 with supported head dim only");
-  return flash_attention_raw(q, k, v, scale, /*bshd=*/true);
+  return flash_attention_raw(q, k, v, scale, /*bshd=*/true, force);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -450,8 +460,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layer_norm", &layer_norm);
   m.def("add_layer_norm", &add_layer_norm);
   m.def("row_softmax_", &row_softmax_);
-  m.def("attention_fwd", &attention_fwd);
-  m.def("attention_fwd_bshd", &attention_fwd_bshd);
+  m.def("attention_fwd", &attention_fwd, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("scale"), py::arg("force") = 0);
+  m.def("attention_fwd_bshd", &attention_fwd_bshd, py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("scale"), py::arg("force") = 0);
+  m.def("attention_plan", &attention_plan);
   m.def("probe_mfma32", &probe_mfma32);
   m.def("probe_mfma16", &probe_mfma16);
   m.def("probe_tr16", &probe_tr16);

@@ -146,13 +146,16 @@ class TestAttention:
         assert err < 0.04, f"attention err {err} at D={D}"
 
     def test_spiked_scores_rescale(self, dev):
-        """Force large max jumps across kv tiles (rule 26: exercise the
-        online-softmax rescale path hard)."""
+        """One late key built from q.mean(dim=2) * 10. That is a mean over
+        256 random rows (sigma ~0.66 per element), an ordinary key: the
+        running max grows ~4 log2 units at the last tile, under v3's
+        defer-max threshold of 8, so no rescale after tile 0 fires. Kept as
+        a plain random-data case; the rescale path itself is tested by
+        tests/test_attention_gpu.py::TestRescale."""
         B, H, S, D = 1, 2, 256, 80
         q = torch.randn(B, H, S, D, device=dev, dtype=torch.bfloat16)
         k = torch.randn(B, H, S, D, device=dev, dtype=torch.bfloat16)
         v = torch.randn(B, H, S, D, device=dev, dtype=torch.bfloat16)
-        # spike one late K row so every q row's max jumps at the last tile
         k[:, :, -1] = q.mean(dim=2) * 10
         scale = 1.0 / math.sqrt(D)
         out = ops.attention(q, k, v)
