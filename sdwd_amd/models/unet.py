@@ -122,7 +122,9 @@ class RegionalContext:
         self.rows = int(rows)         # leading rows blended regionally
         self.base_ratio = float(base_ratio)
         self.lat_hw = lat_hw          # latent grid the masks are drawn on
-        self._cache = {}              # seq_len -> [R, s] pooled masks
+        # seq_len -> [R, s] pooled masks; tuple keys -> the fused route's
+        # blend weights and index tables (CrossAttention._regional_fused)
+        self._cache = {}
 
     def __getitem__(self, sl):
         plain = self.plain[sl]
@@ -172,6 +174,12 @@ class RegionalContext:
 
 
 class CrossAttention(nn.Module):
+    # RegionalContext on the GPU: True blends base and region attentions
+    # inside one kernel (ops.attention_blend_bshd); False keeps the
+    # per-region loop (A/B timing, comparison tests). CPU, non-bf16 tensors
+    # and head dims without a flash kernel take the loop either way.
+    fused_regional = True
+
     def __init__(self, query_dim: int, context_dim: int, heads: int):
         super().__init__()
         self.heads = heads
@@ -204,6 +212,48 @@ class CrossAttention(nn.Module):
             self._wcat_cache = cache = (key, cat, tuple(names))
         return cache[1]
 
+    def _regional_fused(self, q, rc, wkv, s):
+        """Regional blend of the cond rows q [nr, s, H, D] through
+        ops.attention_blend_bshd: context 0 is the row's own base prompt,
+        contexts 1..R the region prompts, shared by every row. One K/V GEMM
+        over [nr+R] contexts replaces the R GEMMs on expanded copies."""
+        import torch.nn.functional as F
+
+        nr, d = q.shape[0], self.heads * self.d_head
+        hd = (self.heads, self.d_head)
+        base, reg = rc.plain[:nr], rc.region_ctx
+        R, lb, lr = reg.shape[0], base.shape[1], reg.shape[1]
+        # base and region prompts are encoded separately and may differ in
+        # token count: zero-pad to the longer, kv_len keeps the true counts
+        smax = max(lb, lr)
+        if lb < smax:
+            base = F.pad(base, (0, 0, 0, smax - lb))
+        if lr < smax:
+            reg = F.pad(reg, (0, 0, 0, smax - lr))
+        kv = F.linear(torch.cat([base, reg.to(base.dtype)], dim=0), wkv)
+        k = kv[..., :d].unflatten(-1, hd)
+        v = kv[..., d:].unflatten(-1, hd)
+        # the class docstring's formula as per-context weights, and the two
+        # small tables, once per shape (rc._cache is shared by row slices)
+        key = ("blend_w", s, q.device)
+        w = rc._cache.get(key)
+        if w is None:
+            m = rc.masks_for(s, q.device, q.dtype)  # [R, s]
+            bw = rc.base_ratio
+            keep = bw + (1.0 - bw) * (1.0 - m.sum(0).clamp(0, 1))
+            w = torch.cat([keep[None], (1.0 - bw) * m], dim=0)[None]
+            rc._cache[key] = w = w.contiguous()
+        key = ("blend_tab", nr, R, lb, lr, q.device)
+        tabs = rc._cache.get(key)
+        if tabs is None:
+            index = [[i] + list(range(nr, nr + R)) for i in range(nr)]
+            lens = [lb] * nr + [lr] * R
+            tabs = (
+                torch.tensor(index, dtype=torch.int32).to(q.device),
+                torch.tensor(lens, dtype=torch.int32).to(q.device),
+            )
+            rc._cache[key] = tabs
+        return ops.attention_blend_bshd(q, k, v, w, tabs[0], tabs[1])
 
     def forward(
         self, x: torch.Tensor, context: Optional[torch.Tensor] = None
@@ -232,9 +282,21 @@ class CrossAttention(nn.Module):
             kv = F.linear(rc.plain, wkv)
             k = kv[..., :d].unflatten(-1, hd)
             v = kv[..., d:].unflatten(-1, hd)
-            out = ops.attention_bshd(q, k, v).reshape(b, s, d)
             nr = rc.rows
-            if nr > 0 and rc.region_ctx is not None:
+            regional = nr > 0 and rc.region_ctx is not None
+            if (regional and self.fused_regional
+                    and ops.attention_blend_supported(q, k, v)):
+                # fused route: base + regions as contexts of ONE blend
+                # kernel over the cond rows. The uncond rows keep the plain
+                # kernel on the K/V of the loop route's own full-batch GEMM
+                # above, which makes them bit-equal between the routes
+                blended = self._regional_fused(q[:nr], rc, wkv, s)
+                if b > nr:
+                    rest = ops.attention_bshd(q[nr:], k[nr:], v[nr:])
+                    blended = torch.cat([blended, rest], dim=0)
+                return self.to_out(blended.reshape(b, s, d))
+            out = ops.attention_bshd(q, k, v).reshape(b, s, d)
+            if regional:
                 m = rc.masks_for(s, x.device, x.dtype)  # [R, s]
                 qr = q[:nr]
                 acc = None

@@ -242,6 +242,143 @@ def attention_bshd(
 
 
 # ---------------------------------------------------------------------------
+# multi-context attention blend (regional prompting, decoupled cross-attn)
+# ---------------------------------------------------------------------------
+def attention_blend_supported(q, k, v) -> bool:
+    """True when attention_blend_bshd runs its kernel on these tensors: on
+    the GPU, bf16, a head dim with a flash kernel, unit stride in D."""
+    return bool(
+        q.is_cuda and k.is_cuda and v.is_cuda
+        and q.dtype == k.dtype == v.dtype == torch.bfloat16
+        and ext().flash_supported(q.shape[-1])
+        and q.stride(-1) == k.stride(-1) == v.stride(-1) == 1
+    )
+
+
+def _blend_table(name, table, shape, lo, hi, device):
+    """A small integer table for the blend kernel as int32 on `device`. A
+    device int32 tensor is taken as it is (the caller validated and cached
+    it); anything else is validated on the host, so no device sync."""
+    if (torch.is_tensor(table) and table.device.type != "cpu"
+            and table.dtype == torch.int32):
+        if tuple(table.shape) != shape:
+            raise ValueError(
+                f"attention_blend: {name} has shape {tuple(table.shape)}, "
+                f"expected {shape}"
+            )
+        if table.device != device:
+            raise ValueError(
+                f"attention_blend: {name} is on {table.device}, q on {device}"
+            )
+        return table.contiguous()
+    if torch.is_tensor(table):
+        if table.device.type != "cpu":
+            raise ValueError(
+                f"attention_blend: a device {name} must be int32 "
+                f"(got {table.dtype})"
+            )
+        if table.dtype.is_floating_point or table.dtype == torch.bool:
+            raise ValueError(f"attention_blend: {name} must hold integers")
+        t = table.to(torch.int64)
+    else:
+        try:
+            t = torch.tensor(table, dtype=torch.int64)
+        except (TypeError, ValueError, RuntimeError) as exc:
+            raise ValueError(
+                f"attention_blend: {name} is not an integer table: {exc}"
+            ) from None
+    if tuple(t.shape) != shape:
+        raise ValueError(
+            f"attention_blend: {name} has shape {tuple(t.shape)}, "
+            f"expected {shape}"
+        )
+    if t.numel() and (int(t.min()) < lo or int(t.max()) > hi):
+        raise ValueError(
+            f"attention_blend: {name} entries must lie in [{lo}, {hi}] "
+            f"(got {int(t.min())}..{int(t.max())})"
+        )
+    return t.to(torch.int32).contiguous().to(device)
+
+
+def attention_blend_bshd(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    w: torch.Tensor,
+    kv_index,
+    kv_len=None,
+    scale: Optional[float] = None,
+) -> torch.Tensor:
+    """Weighted sum of attentions that share Q, in one kernel:
+
+        out[b,s,h,:] = sum_c w[b,c,s] * softmax(scale * q[b,s,h] K_c^T) V_c
+
+    with K_c, V_c = k[kv_index[b][c]], v[kv_index[b][c]] cut to their first
+    kv_len[kv_index[b][c]] keys. q [B,Sq,H,D]; k, v [Bk,Sk,H,D] (strided
+    views with unit stride in D, as attention_bshd takes); w fp32 [B,C,Sq]
+    or [1,C,Sq]; kv_index [B,C] and kv_len [Bk] (None: all Sk keys) are CPU
+    integer tensors or lists, validated here without a device sync, or
+    device int32 tensors, taken unvalidated so a caller can cache them.
+
+    GPU path: flash_blend_bf16_kernel (ops/hip/attention.hip): per-context
+    online softmax, fp32 blend in registers, one bf16 rounding. bf16 and a
+    head dim with a flash kernel only; anything else raises, the blend is
+    never composed from separate attentions.
+    CPU path: plain fp32 reference (the numerics oracle).
+    """
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dim() != 4:
+            raise ValueError(f"attention_blend: {name} must be [B, S, H, D]")
+    B, Sq, H, D = q.shape
+    Bk, Sk = k.shape[0], k.shape[1]
+    if tuple(k.shape) != tuple(v.shape):
+        raise ValueError("attention_blend: k and v shapes differ")
+    if Bk < 1 or Sk < 1 or B < 1 or Sq < 1:
+        raise ValueError("attention_blend: q, k and v must be non-empty")
+    if tuple(k.shape[2:]) != (H, D):
+        raise ValueError(
+            f"attention_blend: k has heads/dim {tuple(k.shape[2:])}, "
+            f"q has {(H, D)}"
+        )
+    if not torch.is_tensor(w) or w.dim() != 3 or w.dtype != torch.float32:
+        raise ValueError("attention_blend: w must be an fp32 [B, C, Sq] tensor")
+    C = w.shape[1]
+    if C < 1:
+        raise ValueError("attention_blend: w needs at least one context (C >= 1)")
+    if w.shape[0] not in (1, B) or w.shape[2] != Sq:
+        raise ValueError(
+            f"attention_blend: w has shape {tuple(w.shape)}, expected "
+            f"[{B} or 1, C, {Sq}]"
+        )
+    if w.device != q.device or k.device != q.device or v.device != q.device:
+        raise ValueError("attention_blend: q, k, v and w must share a device")
+    idx = _blend_table("kv_index", kv_index, (B, C), 0, Bk - 1, q.device)
+    lens = None
+    if kv_len is not None:
+        lens = _blend_table("kv_len", kv_len, (Bk,), 1, Sk, q.device)
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if q.is_cuda:
+        if w.stride(2) != 1:
+            w = w.contiguous()
+        return ext().attention_blend_bshd(q, k, v, w, idx, lens, scale)
+    idx = idx.tolist()
+    lens = [Sk] * Bk if lens is None else lens.tolist()
+    qf = q.float().permute(0, 2, 1, 3)                    # [B, H, Sq, D]
+    out = torch.zeros(B, H, Sq, D, dtype=torch.float32)
+    for b in range(B):
+        wb = w[b if w.shape[0] > 1 else 0]
+        for c in range(C):
+            row = idx[b][c]
+            n = lens[row]
+            kf = k[row, :n].float().permute(1, 0, 2)      # [H, n, D]
+            vf = v[row, :n].float().permute(1, 0, 2)
+            p = torch.softmax(qf[b] @ kf.transpose(-1, -2) * scale, dim=-1)
+            out[b] += wb[c][None, :, None] * (p @ vf)
+    return out.permute(0, 2, 1, 3).to(q.dtype)
+
+
+# ---------------------------------------------------------------------------
 # GEGLU activation: x, gate = split(h); x * gelu(gate)
 # ---------------------------------------------------------------------------
 def geglu(h: torch.Tensor) -> torch.Tensor:

@@ -567,6 +567,240 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
 }
 
 // ---------------------------------------------------------------------------
+// multi-context blend: out[b,s,h,:] = sum_c W[b,c,s] * attn(q[b,s,h], K_c, V_c)
+// with K_c/V_c = batch row kv_index[b*C + c] of K/V, kv_len[row] keys long.
+// The v2 kernel (4 waves, 64-key LDS tiles, swapped QK^T, in-register
+// softmax, permlane P relayout, fp32 score scaling after the MFMA) with a
+// context loop around the tile loop: Q fragments are read once; every
+// context restarts m/l/o, walks its own tiles, and folds o * (w / l) into
+// a second fp32 accumulator; the output is rounded to bf16 once, after the
+// last context. The row and its length depend on (b, c) only, so every
+// wave of the block walks every context and every tile and the barriers
+// stay block-uniform. No zero-weight shortcut: every context is computed.
+// Registers: o and acc are 2 * QS * ND * 16 fp32 next to NC * QS * 4 of Q
+// fragments and 32 of scores. Two blocks per CU leave 256 registers a lane:
+// QS=2 fits only at DPAD 32, QS=1 (128 q rows per block) up to DPAD 96.
+// Beyond that they do not (at DPAD 192 o, acc, Q and the scores alone are
+// 272), so DPAD >= 112 runs one block per CU with AGPRs. No instantiation uses
+// scratch (checked with -Rpass-analysis=kernel-resource-usage; table in
+// docs/kernels.md).
+// ---------------------------------------------------------------------------
+constexpr int blend_qs(int dpad) { return dpad <= 32 ? 2 : 1; }
+constexpr int blend_min_blocks(int dpad) { return dpad <= 96 ? 2 : 1; }
+
+template <int DPAD, int QS = blend_qs(DPAD)>
+__launch_bounds__(256, blend_min_blocks(DPAD)) __global__
+void flash_blend_bf16_kernel(
+    const __hip_bfloat16 *__restrict__ Q, const __hip_bfloat16 *__restrict__ K,
+    const __hip_bfloat16 *__restrict__ V, __hip_bfloat16 *__restrict__ O,
+    int H, long Sq, long Sk, int D, float scale, AttnStrides st, int C,
+    int Bk, const int *__restrict__ kv_index, const int *__restrict__ kv_len,
+    const float *__restrict__ W, long wb, long wc) {
+  constexpr int KVB = 64;
+  constexpr int PADK = 8;
+  constexpr int NC = DPAD / 16;
+  constexpr int DV = (DPAD + 31) / 32 * 32;
+  constexpr int ND = DV / 32;
+
+  __shared__ __align__(16) __bf16 kt[KVB][DPAD + PADK];
+  __shared__ __align__(16) __bf16 vt[DV][KVB + PADK];
+
+  const int bh = blockIdx.y;
+  const int qblk = blockIdx.x;
+  const int bb = bh / H, hh = bh % H;
+  const int wid = threadIdx.x / WAVE;
+  const int lane = threadIdx.x % WAVE;
+  const int lq = lane % 32;
+  const int half = lane / 32;
+  const long q0 = (long)qblk * (QS * 128) + wid * (QS * 32);
+
+  const __hip_bfloat16 *Qb = Q + bb * st.qb + hh * st.qh;
+  __hip_bfloat16 *Ob = O + bb * st.ob + hh * st.oh;
+
+  bf16x8 qf[QS][NC];
+#pragma unroll
+  for (int qs = 0; qs < QS; ++qs) {
+    const long qq = q0 + qs * 32 + lq;
+    const long qrow = (qq < Sq) ? qq : (Sq - 1);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int d0 = c * 16 + 8 * half;
+      qf[qs][c] = (d0 + 8 <= D)
+                      ? *(const bf16x8 *)(Qb + qrow * st.qr + d0)
+                      : (bf16x8){};
+    }
+  }
+
+  f32x16 acc[QS][ND];
+#pragma unroll
+  for (int qs = 0; qs < QS; ++qs)
+#pragma unroll
+    for (int d = 0; d < ND; ++d) acc[qs][d] = (f32x16){};
+
+  // zero vt's pad rows once (D..DV); they are never re-staged
+  for (int idx = threadIdx.x + (D / 8) * 8 * (KVB + PADK);
+       idx < DV * (KVB + PADK); idx += 256)
+    ((__bf16 *)vt)[idx] = (__bf16)0.0f;
+
+  const float l2scale = scale * 1.4426950408889634f;
+
+  for (int cx = 0; cx < C; ++cx) {
+    // block-uniform: the K/V row of (b, context) and its key count. The
+    // wrapper validates host tables; the clamps keep a bad device table
+    // inside the K/V allocation
+    int row = kv_index[bb * C + cx];
+    row = row < 0 ? 0 : (row >= Bk ? Bk - 1 : row);
+    long len = kv_len ? (long)kv_len[row] : Sk;
+    len = len < 0 ? 0 : (len > Sk ? Sk : len);
+    const __hip_bfloat16 *Kb = K + row * st.kb + hh * st.kh;
+    const __hip_bfloat16 *Vb = V + row * st.vb + hh * st.vh;
+
+    f32x16 o[QS][ND];
+#pragma unroll
+    for (int qs = 0; qs < QS; ++qs)
+#pragma unroll
+      for (int d = 0; d < ND; ++d) o[qs][d] = (f32x16){};
+    float m[QS], l[QS];
+#pragma unroll
+    for (int qs = 0; qs < QS; ++qs) { m[qs] = -1e30f; l[qs] = 0.f; }
+
+    for (long kv = 0; kv < len; kv += KVB) {
+      __syncthreads();  // previous tile's (or context's) LDS reads complete
+      for (int idx = threadIdx.x; idx < KVB * (DPAD / 8); idx += 256) {
+        const int r = idx / (DPAD / 8);
+        const int c8 = idx % (DPAD / 8);
+        bf16x8 kvec = (bf16x8){};
+        bf16x8 vvec = (bf16x8){};
+        if (kv + r < len && c8 * 8 + 8 <= D) {
+          kvec = *(const bf16x8 *)(Kb + (kv + r) * st.kr + c8 * 8);
+          vvec = *(const bf16x8 *)(Vb + (kv + r) * st.vr + c8 * 8);
+        }
+        *(bf16x8 *)&kt[r][c8 * 8] = kvec;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) vt[c8 * 8 + j][r] = vvec[j];
+      }
+      __syncthreads();
+
+#pragma unroll
+      for (int qs = 0; qs < QS; ++qs) {
+        f32x16 stile[2] = {(f32x16){}, (f32x16){}};
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            bf16x8 kf =
+                *(const bf16x8 *)&kt[sub * 32 + lq][c * 16 + 8 * half];
+            stile[sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                kf, qf[qs][c], stile[sub], 0, 0, 0);
+          }
+
+        // base-2 softmax in the accumulator registers; the fp32 scores
+        // are scaled here, after the MFMA (Q is not pre-scaled)
+        float pmax = -1e30f;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int kk = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const float sv =
+                (kv + kk < len) ? stile[sub][r] * l2scale : -1e30f;
+            stile[sub][r] = sv;
+            pmax = fmaxf(pmax, sv);
+          }
+        pmax = fmaxf(pmax, __shfl_xor(pmax, 32, WAVE));
+        const float mnew = fmaxf(m[qs], pmax);
+        const float alpha = __builtin_amdgcn_exp2f(m[qs] - mnew);
+        float rowsum = 0.f;
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            stile[sub][r] = __builtin_amdgcn_exp2f(stile[sub][r] - mnew);
+            rowsum += stile[sub][r];
+          }
+        rowsum += __shfl_xor(rowsum, 32, WAVE);
+        l[qs] = l[qs] * alpha + rowsum;
+        m[qs] = mnew;
+
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int qrow = (r & 3) + 8 * (r >> 2) + 4 * half;
+          const float a = __shfl(alpha, qrow, WAVE);
+#pragma unroll
+          for (int d = 0; d < ND; ++d) o[qs][d][r] *= a;
+        }
+
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+          unsigned pk[8];
+#pragma unroll
+          for (int t = 0; t < 8; ++t)
+            pk[t] = pack_bf16(stile[sub][2 * t], stile[sub][2 * t + 1]);
+          bf16x8 pa0, pa1;
+          {
+            auto r0 =
+                __builtin_amdgcn_permlane32_swap(pk[0], pk[2], false, false);
+            auto r1 =
+                __builtin_amdgcn_permlane32_swap(pk[1], pk[3], false, false);
+            unsigned frag[4] = {r0[0], r1[0], r0[1], r1[1]};
+            pa0 = *(bf16x8 *)frag;
+            auto r2 =
+                __builtin_amdgcn_permlane32_swap(pk[4], pk[6], false, false);
+            auto r3 =
+                __builtin_amdgcn_permlane32_swap(pk[5], pk[7], false, false);
+            unsigned frag1[4] = {r2[0], r3[0], r2[1], r3[1]};
+            pa1 = *(bf16x8 *)frag1;
+          }
+#pragma unroll
+          for (int d = 0; d < ND; ++d) {
+            bf16x8 v0 =
+                *(const bf16x8 *)&vt[d * 32 + lq][sub * 32 + 8 * half];
+            o[qs][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                pa0, v0, o[qs][d], 0, 0, 0);
+            bf16x8 v1 =
+                *(const bf16x8 *)&vt[d * 32 + lq][sub * 32 + 16 + 8 * half];
+            o[qs][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+                pa1, v1, o[qs][d], 0, 0, 0);
+          }
+        }
+      }
+    }
+
+    // fold this context in: acc += o * (w / l). Lane lq holds its own
+    // row's l and loads its own row's weight; the per-row lane broadcast
+    // is the one the 1/l epilogue uses
+#pragma unroll
+    for (int qs = 0; qs < QS; ++qs) {
+      const long qq = q0 + qs * 32 + lq;
+      const float wv = (qq < Sq) ? W[bb * wb + cx * wc + qq] : 0.f;
+      const float wl = wv / fmaxf(l[qs], 1e-30f);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int qrow = (r & 3) + 8 * (r >> 2) + 4 * half;
+        const float f = __shfl(wl, qrow, WAVE);
+#pragma unroll
+        for (int d = 0; d < ND; ++d) acc[qs][d][r] += o[qs][d][r] * f;
+      }
+    }
+  }
+
+  // one bf16 rounding of the blended row
+#pragma unroll
+  for (int qs = 0; qs < QS; ++qs) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int qrow = (r & 3) + 8 * (r >> 2) + 4 * half;
+      const long qq = q0 + qs * 32 + qrow;
+      if (qq >= Sq) continue;
+#pragma unroll
+      for (int d = 0; d < ND; ++d)
+        if (d * 32 + lq < D)
+          Ob[qq * st.or_ + d * 32 + lq] = f2bf(acc[qs][d][r]);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // host-side dispatch (torch API lives in ext.hip which includes this file)
 // ---------------------------------------------------------------------------
 bool flash_supported(long d_head) {
@@ -674,6 +908,75 @@ static torch::Tensor flash_attention_raw(torch::Tensor q, torch::Tensor k,
     default: TORCH_CHECK(false, "flash: unsupported padded head dim ", DP);
   }
 #undef LAUNCH_FLASH
+  return out;
+}
+
+// The multi-context blend kernel's geometry: {padded head dim, q rows per
+// workgroup}. One kernel family serves every supported head dim; a head
+// dim without a flash kernel is an error (the blend is never composed).
+// The launcher below follows this and nothing else decides.
+std::tuple<long, long> attention_blend_plan(long d_head) {
+  TORCH_CHECK(flash_supported(d_head), "attention_blend: head dim ", d_head,
+              " has no flash kernel");
+  const long dpad = round16(d_head);
+  return {dpad, 128 * blend_qs((int)dpad)};
+}
+
+// q [B,Sq,H,D], k/v [Bk,Sk,H,D] (unit stride in D, 16-byte-aligned rows),
+// w fp32 [B or 1, C, Sq] unit-stride in s, kv_index int32 [B*C] and kv_len
+// int32 [Bk] (or undefined) on the device.
+static torch::Tensor flash_blend_raw(torch::Tensor q, torch::Tensor k,
+                                     torch::Tensor v, torch::Tensor w,
+                                     torch::Tensor kv_index,
+                                     c10::optional<torch::Tensor> kv_len,
+                                     double scale) {
+  const long B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3);
+  const long Bk = k.size(0), Sk = k.size(1);
+  const long C = w.size(1);
+  auto out = torch::empty({B, Sq, H, D}, q.options());
+  AttnStrides st;
+  st.qb = q.stride(0); st.qh = q.stride(2); st.qr = q.stride(1);
+  st.kb = k.stride(0); st.kh = k.stride(2); st.kr = k.stride(1);
+  st.vb = v.stride(0); st.vh = v.stride(2); st.vr = v.stride(1);
+  st.ob = out.stride(0); st.oh = out.stride(2); st.or_ = out.stride(1);
+  const long wb = w.size(0) == 1 ? 0 : w.stride(0), wc = w.stride(1);
+  const auto [DP, qrows] = attention_blend_plan(D);
+  const dim3 grid((unsigned)((Sq + qrows - 1) / qrows), (unsigned)(B * H));
+  const dim3 block(256);
+  auto stream = cur_stream();
+  const int *len_ptr =
+      kv_len.has_value() ? kv_len->data_ptr<int>() : (const int *)nullptr;
+
+#define LAUNCH_BLEND(DP_)                                                   \
+  do {                                                                      \
+    TORCH_CHECK(qrows == 128 * blend_qs(DP_),                               \
+                "flash_blend: plan rows do not match the instantiation");   \
+    hipLaunchKernelGGL(flash_blend_bf16_kernel<DP_>, grid, block, 0,        \
+                       stream, (const __hip_bfloat16 *)q.data_ptr(),        \
+                       (const __hip_bfloat16 *)k.data_ptr(),                \
+                       (const __hip_bfloat16 *)v.data_ptr(),                \
+                       (__hip_bfloat16 *)out.data_ptr(), (int)H, Sq, Sk,    \
+                       (int)D, (float)scale, st, (int)C, (int)Bk,           \
+                       kv_index.data_ptr<int>(), len_ptr,                   \
+                       w.data_ptr<float>(), wb, wc);                        \
+  } while (0)
+
+  switch (DP) {
+    case 32: LAUNCH_BLEND(32); break;
+    case 48: LAUNCH_BLEND(48); break;
+    case 64: LAUNCH_BLEND(64); break;
+    case 80: LAUNCH_BLEND(80); break;
+    case 96: LAUNCH_BLEND(96); break;
+    case 112: LAUNCH_BLEND(112); break;
+    case 128: LAUNCH_BLEND(128); break;
+    case 144: LAUNCH_BLEND(144); break;
+    case 160: LAUNCH_BLEND(160); break;
+    case 176: LAUNCH_BLEND(176); break;
+    case 192: LAUNCH_BLEND(192); break;
+    default:
+      TORCH_CHECK(false, "flash_blend: unsupported padded head dim ", DP);
+  }
+#undef LAUNCH_BLEND
   return out;
 }
 

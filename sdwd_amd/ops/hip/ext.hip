@@ -448,6 +448,54 @@ torch::Tensor attention_fwd_bshd(torch::Tensor q, torch::Tensor k,
   return flash_attention_raw(q, k, v, scale, /*bshd=*/true, force);
 }
 
+torch::Tensor attention_blend_bshd(torch::Tensor q, torch::Tensor k,
+                                   torch::Tensor v, torch::Tensor w,
+                                   torch::Tensor kv_index,
+                                   c10::optional<torch::Tensor> kv_len,
+                                   double scale) {
+  // sum_c w[b,c,s] * attention(q[b], k[kv_index[b,c]], v[kv_index[b,c]]);
+  // the Python wrapper validates the table VALUES, this checks everything
+  // the launch itself depends on
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4,
+              "attention_blend: q/k/v must be [B,S,H,D]");
+  TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda() && w.is_cuda() &&
+                  kv_index.is_cuda(),
+              "attention_blend: tensors must be on the GPU");
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16 &&
+                  k.scalar_type() == torch::kBFloat16 &&
+                  v.scalar_type() == torch::kBFloat16 &&
+                  flash_supported(q.size(3)),
+              "attention_blend: bf16 with supported head dim only");
+  const long B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3);
+  TORCH_CHECK(B > 0 && Sq > 0 && H > 0 && k.size(0) > 0 && k.size(1) > 0,
+              "attention_blend: empty q/k/v");
+  TORCH_CHECK(k.sizes() == v.sizes() && k.size(2) == H && k.size(3) == D,
+              "attention_blend: k/v shape mismatch");
+  for (const auto &t : {q, k, v}) {
+    bool rows16 = t.stride(3) == 1 && ((uintptr_t)t.data_ptr()) % 16 == 0;
+    for (int i = 0; i < 3; ++i)
+      rows16 = rows16 && (t.size(i) == 1 || t.stride(i) % 8 == 0);
+    TORCH_CHECK(rows16,
+                "attention_blend: q/k/v need unit stride in D and "
+                "16-byte-aligned rows");
+  }
+  TORCH_CHECK(w.scalar_type() == torch::kFloat && w.dim() == 3 &&
+                  (w.size(0) == B || w.size(0) == 1) && w.size(1) >= 1 &&
+                  w.size(2) == Sq && w.stride(2) == 1,
+              "attention_blend: w must be fp32 [B or 1, C, Sq], unit stride "
+              "in Sq");
+  const long C = w.size(1);
+  TORCH_CHECK(kv_index.scalar_type() == torch::kInt &&
+                  kv_index.is_contiguous() && kv_index.numel() == B * C,
+              "attention_blend: kv_index must be contiguous int32 [B, C]");
+  if (kv_len.has_value()) {
+    TORCH_CHECK(kv_len->is_cuda() && kv_len->scalar_type() == torch::kInt &&
+                    kv_len->is_contiguous() && kv_len->numel() == k.size(0),
+                "attention_blend: kv_len must be contiguous int32 [Bk]");
+  }
+  return flash_blend_raw(q, k, v, w, kv_index, kv_len, scale);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("silu", &silu);
   m.def("geglu", &geglu);
@@ -465,6 +513,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_fwd_bshd", &attention_fwd_bshd, py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("scale"), py::arg("force") = 0);
   m.def("attention_plan", &attention_plan);
+  m.def("attention_blend_bshd", &attention_blend_bshd, py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("w"), py::arg("kv_index"),
+        py::arg("kv_len"), py::arg("scale"));
+  m.def("attention_blend_plan", &attention_blend_plan);
   m.def("probe_mfma32", &probe_mfma32);
   m.def("probe_mfma16", &probe_mfma16);
   m.def("probe_tr16", &probe_tr16);
