@@ -82,6 +82,9 @@ class SDConv2d(nn.Conv2d):
     # False sends circular convs on the GPU back to F.pad + the library
     # conv (A/B timing and the end-to-end comparison test)
     native_circular = True
+    # False keeps forward_upsampled2x on the 9-tap fused kernel instead of
+    # the four folded 2x2 sub-pixel convs (A/B timing)
+    fold_upsample = True
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -96,9 +99,20 @@ class SDConv2d(nn.Conv2d):
             or cache[1] != w.dtype
         ):
             prep = w.permute(0, 2, 3, 1).contiguous()  # [Cout,3,3,Cin]
-            self._wprep_cache = ((w.data_ptr(), w._version), w.dtype, prep)
+            # slot 3: the folded weights of an upsampling conv (_wfold)
+            self._wprep_cache = [(w.data_ptr(), w._version), w.dtype, prep,
+                                 None]
             return prep
         return cache[2]
+
+    def _wfold(self) -> torch.Tensor:
+        """ops.fold_ups2x_weight(_wprep()), kept in _wprep's cache entry
+        under its key: whatever invalidates one invalidates both."""
+        prep = self._wprep()
+        cache = self._wprep_cache
+        if cache[3] is None:
+            cache[3] = ops.fold_ups2x_weight(prep)
+        return cache[3]
 
     def _wrap_axes(self) -> tuple[bool, bool]:
         """(wrap_h, wrap_w) from `circular`: True wraps both axes (what the
@@ -125,8 +139,10 @@ class SDConv2d(nn.Conv2d):
             from .. import ops
 
             xc = x.contiguous(memory_format=torch.channels_last)
+            fold = self.fold_upsample
             return ops.ups2x_conv3x3(
-                xc, self._wprep(), self.bias, collect_gn=True, wrap=wrap
+                xc, self._wprep(), self.bias, collect_gn=True, wrap=wrap,
+                w_fold=self._wfold() if fold else None, fold=fold,
             )
         x = torch.nn.functional.interpolate(
             x, scale_factor=2, mode="nearest"

@@ -592,18 +592,54 @@ def conv3x3_small_supported(cin: int, cout: int) -> bool:
     )
 
 
+def fold_ups2x_weight(
+    w_prep: torch.Tensor, out: Optional[torch.Tensor] = None
+) -> torch.Tensor:
+    """[Cout,3,3,Cin] -> [4,Cout,2,2,Cin]: the 3x3 weights folded for a conv
+    over a nearest-2x upsample. Output pixel (2i+a, 2j+b) sees source rows
+    i-1+a+r, r in {0,1}: phase a=0 weighs them w[0], w[1]+w[2]; a=1 weighs
+    them w[0]+w[1], w[2]; columns alike with b, s, kx. Entry p = 2a+b is
+    that phase's 2x2 kernel. The sums are formed in fp32 (fp64 for fp64
+    input), rows first, in a fixed order, and rounded once to w_prep's
+    dtype; `out` is refilled in place. The only implementation of the
+    fold, for CPU and GPU tensors."""
+    w = w_prep.double() if w_prep.dtype == torch.float64 else w_prep.float()
+    k0, k1, k2 = w[:, 0], w[:, 1], w[:, 2]  # [Cout,3(kx),Cin]
+    rows = torch.stack(  # [2(a),Cout,2(r),3(kx),Cin]
+        [torch.stack([k0, k1 + k2], 1), torch.stack([k0 + k1, k2], 1)]
+    )
+    c0, c1, c2 = rows[..., 0, :], rows[..., 1, :], rows[..., 2, :]
+    fold = torch.stack(  # [2(a),2(b),Cout,2(r),2(s),Cin]
+        [torch.stack([c0, c1 + c2], -2), torch.stack([c0 + c1, c2], -2)], 1
+    )
+    fold = fold.reshape(4, *fold.shape[2:]).to(w_prep.dtype)
+    if out is not None:
+        out.copy_(fold)
+        return out
+    return fold.contiguous()
+
+
 def ups2x_conv3x3(
     x: torch.Tensor,
     w_prep: torch.Tensor,
     bias: Optional[torch.Tensor],
     collect_gn: bool = False,
     wrap: Tuple[bool, bool] = (False, False),
+    w_fold: Optional[torch.Tensor] = None,
+    fold: bool = True,
 ) -> torch.Tensor:
     """Nearest-2x upsample fused into a 3x3 conv (VAE decoder / UNet
     Upsample): no 4x intermediate tensor. wrap = (height, width) wraps the
-    conv's padding around the upsampled image. GPU-only entry."""
+    conv's padding around the upsampled image. fold (the default) runs it
+    as four 2x2 sub-pixel convs on the source image with the folded weights
+    w_fold (fold_ups2x_weight(w_prep); computed here when absent - callers
+    on a hot path cache it): 2.25x fewer FLOPs. fold=False keeps the 9-tap
+    kernel. GPU-only entry."""
+    if fold and w_fold is None:
+        w_fold = fold_ups2x_weight(w_prep)
     y, gnp = ext().ups2x_conv3x3(
-        x, w_prep, bias, collect_gn, bool(wrap[0]), bool(wrap[1])
+        x, w_prep, bias, collect_gn, bool(wrap[0]), bool(wrap[1]),
+        w_fold if fold else None, bool(fold),
     )
     _attach_gn_partials(y, gnp)
     return y

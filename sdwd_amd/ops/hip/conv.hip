@@ -22,6 +22,8 @@
 //  * WRAP instantiations (seamless tiling) instead fold an out-of-image
 //    tap back onto the opposite border, per axis (wrap_h / wrap_w): only
 //    the DMA source address differs, an unwrapped axis keeps the zero page;
+//  * FOLD instantiations run conv(nearest2x(x)) as four 2x2 sub-pixel convs
+//    on the source image with pre-summed weights (K = 4*Cin, not 9*Cin);
 //  * bias, per-(sample,channel) bias (time embedding) and the ResBlock
 //    residual add are fused into the epilogue.
 //
@@ -55,8 +57,19 @@ typedef __attribute__((ext_vector_type(4))) float f32x4c;
 // WRAP: "may wrap" - the border taps of an axis whose wrap_h / wrap_w flag is
 // set read the opposite border instead of the zero page (on the virtual
 // 2H x 2W grid for UPS). WRAP=false compiles the flags away.
+// FOLD: the same fused upsample+conv as UPS, computed as four 2x2 sub-pixel
+// convs on the SOURCE image. The 3 virtual rows (columns) a 3x3 window
+// touches come from 2 source rows (columns), so output phase
+// p = 2a + b = 2(oh&1) + (ow&1) is a 2x2 conv whose weights are sums of the
+// 3x3 weights: Wt is the folded [4][Cout][2][2][Cin] (fold_ups2x_weight).
+// GEMM rows are the N*H*W source pixels of ONE phase, K = 4*Cin (2.25x
+// fewer FLOPs than UPS); M-tile index = 4*(tile in phase) + p, so the four
+// phases of a source tile are dispatched together and share A in L2. Tap
+// (r,s) of source pixel (i,j) reads X[i-1+a+r][j-1+b+s]: the plain
+// addressing with a shifted base, so zero padding and WRAP (on the source
+// grid, which equals wrapping the virtual one) are the non-UPS code paths.
 template <bool HAS_BIAS, bool HAS_RES, bool HAS_CB, int BN = 128,
-          bool UPS = false, bool WRAP = false>
+          bool UPS = false, bool WRAP = false, bool FOLD = false>
 __launch_bounds__(256, 2) __global__ void conv3x3_nhwc_bf16_kernel(
     const __hip_bfloat16 *__restrict__ X,   // [N,H,W,Cin]
     const __hip_bfloat16 *__restrict__ Wt,  // [Cout,3,3,Cin]
@@ -76,14 +89,24 @@ __launch_bounds__(256, 2) __global__ void conv3x3_nhwc_bf16_kernel(
   // one __shared__ object: [buf0: A(8K elems) B(8K)][buf1: A B]
   __shared__ __align__(16) __bf16 smem[4 * TILE_ELEMS];
 
-  const long M = (long)Nn * Ho * Wo;
+  static_assert(!(UPS && FOLD) && !(FOLD && (HAS_RES || HAS_CB)));
+  const long M = FOLD ? (long)Nn * H * W : (long)Nn * Ho * Wo;
   // grid: x = Cout tiles, y (+z overflow) = M tiles, so consecutively-
   // dispatched blocks are the column tiles of ONE row tile and share its
   // A reads in L2/L3
   constexpr int NJ = BN / 32;          // 4 or 2 column fragments per wave
   constexpr int BTILE = BN * CONV_BK;  // B-tile elements
+  // FOLD: M-tile index = 4 * (tile in phase) + 2a + b
+  const int fa = FOLD ? (blockIdx.y >> 1) & 1 : 0;  // output row phase
+  const int fb = FOLD ? blockIdx.y & 1 : 0;         // output column phase
   const long m0 =
-      ((long)blockIdx.y + (long)blockIdx.z * 32768) * CONV_BM;
+      (((long)blockIdx.y + (long)blockIdx.z * 32768) >> (FOLD ? 2 : 0)) *
+      CONV_BM;
+  if constexpr (FOLD) {
+    // a grid spilling into z rounds the tile count up: nothing to do there
+    // (and no partial slot to write)
+    if (m0 >= M) return;
+  }
   const int n0 = blockIdx.x * BN;
 
   const int tid = threadIdx.x;
@@ -106,18 +129,27 @@ __launch_bounds__(256, 2) __global__ void conv3x3_nhwc_bf16_kernel(
     const int row = i * 32 + wid * 8 + lane / 8;
     const long m = m0 + row;
     const long mm = (m < M) ? m : (M - 1);
-    const int n_img = (int)(mm / ((long)Ho * Wo));
-    const int rem = (int)(mm % ((long)Ho * Wo));
-    hs[i] = (rem / Wo) * stride;
-    ws[i] = (rem % Wo) * stride;
-    nimg[i] = n_img;
-    abase[i] = (((long)n_img * H + hs[i]) * W + ws[i]) * Cin;
+    if constexpr (FOLD) {
+      // mm is the source pixel's linear index; (hs, ws) = its tap (0,0)
+      const unsigned q = (unsigned)mm / (unsigned)W;  // n*H + i (host: int)
+      hs[i] = (int)(q % (unsigned)H) - 1 + fa;
+      ws[i] = (int)((unsigned)mm - q * (unsigned)W) - 1 + fb;
+      nimg[i] = 0;
+      abase[i] = (mm + (long)(fa - 1) * W + (fb - 1)) * Cin;
+    } else {
+      const int n_img = (int)(mm / ((long)Ho * Wo));
+      const int rem = (int)(mm % ((long)Ho * Wo));
+      hs[i] = (rem / Wo) * stride;
+      ws[i] = (rem % Wo) * stride;
+      nimg[i] = n_img;
+      abase[i] = (((long)n_img * H + hs[i]) * W + ws[i]) * Cin;
+    }
     bco[i] = n0 + row;
   }
   const int schunk = lane % 8;
 
   const int kc_per_plane = Cin / CONV_BK;
-  const int NT = 9 * kc_per_plane;
+  const int NT = (FOLD ? 4 : 9) * kc_per_plane;
   // WRAP: what folding a tap back adds to its address (host checks int)
   const int row_elems = W * Cin, img_elems = H * row_elems;
   (void)row_elems;
@@ -127,7 +159,9 @@ __launch_bounds__(256, 2) __global__ void conv3x3_nhwc_bf16_kernel(
   auto stage = [&](int t, int b) {
     const int plane = t / kc_per_plane;
     const int kc = t % kc_per_plane;
-    const int dy = plane / 3 - 1, dx = plane % 3 - 1;
+    // FOLD: plane = 2r + s, the tap offset from (hs, ws) is (r, s)
+    const int dy = FOLD ? plane >> 1 : plane / 3 - 1;
+    const int dx = FOLD ? plane & 1 : plane % 3 - 1;
     const long poff = ((long)dy * W + dx) * Cin + (long)kc * CONV_BK;
     __bf16 *abuf = smem + b * (TILE_ELEMS + BTILE);
     __bf16 *bbuf = abuf + TILE_ELEMS;
@@ -190,10 +224,19 @@ __launch_bounds__(256, 2) __global__ void conv3x3_nhwc_bf16_kernel(
           16, 0, 0);
       if (i < NB) {
         const bool bv = bco[i] < Cout;
-        const __hip_bfloat16 *bsrc =
-            bv ? (Wt + (long)bco[i] * 9 * Cin + plane * Cin +
-                  kc * CONV_BK + sc * 8)
-               : Zero;
+        const __hip_bfloat16 *bsrc;
+        if constexpr (FOLD) {
+          // phase p's [Cout][2][2][Cin] matrix (Cout = all columns)
+          bsrc = bv ? (Wt +
+                       (((long)(2 * fa + fb) * Cout + bco[i]) * 4 + plane) *
+                           Cin +
+                       kc * CONV_BK + sc * 8)
+                    : Zero;
+        } else {
+          bsrc = bv ? (Wt + (long)bco[i] * 9 * Cin + plane * Cin +
+                       kc * CONV_BK + sc * 8)
+                    : Zero;
+        }
         __builtin_amdgcn_global_load_lds(
             (const __attribute__((address_space(1))) unsigned int *)bsrc,
             (__attribute__((address_space(3))) unsigned int
@@ -269,8 +312,15 @@ __launch_bounds__(256, 2) __global__ void conv3x3_nhwc_bf16_kernel(
       const float bv = HAS_BIAS ? bias[co] : 0.0f;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const long m = m0 + wm + i * 16 + r4 + r;
+        long m = m0 + wm + i * 16 + r4 + r;
         if (m >= M) continue;
+        if constexpr (FOLD) {
+          // source pixel (n, i, j) -> output row (n, 2i+a, 2j+b); with
+          // q = n*H + i, n*Ho + 2i is 2q
+          const unsigned q = (unsigned)m / (unsigned)W;
+          const unsigned jw = (unsigned)m - q * (unsigned)W;
+          m = (long)(2 * q + fa) * Wo + 2 * jw + fb;
+        }
         float v = acc[i][j][r] + bv;
         if (HAS_CB) {
           const int ni = (int)(m / ((long)Ho * Wo));
@@ -307,7 +357,14 @@ __launch_bounds__(256, 2) __global__ void conv3x3_nhwc_bf16_kernel(
     __syncthreads();
     // fixed-order cross-wave combine: col c's two waves are
     // {c/(BN/2), +2} (wave grid 2Mx2N); one thread per column writes
-    const long mtile = (long)blockIdx.y + (long)blockIdx.z * 32768;
+    // FOLD (host enables only when H*W % BM == 0): a tile lies in one
+    // (image, phase); the image's Ho*Wo/BM slots are [phase][tile], any
+    // partition of its pixels serves gn_nhwc_stats
+    long gslot = (long)blockIdx.y + (long)blockIdx.z * 32768;
+    if constexpr (FOLD) {
+      const long tps = ((long)H * W) / CONV_BM, tp = gslot >> 2;
+      gslot = ((tp / tps) * 4 + (gslot & 3)) * tps + tp % tps;
+    }
     for (int c = tid; c < BN; c += 256) {
       const int co = n0 + c;
       if (co >= Cout) continue;
@@ -316,7 +373,7 @@ __launch_bounds__(256, 2) __global__ void conv3x3_nhwc_bf16_kernel(
       const int lc = c % 16;
       const float *s0 = lds + ((h * NJ + jj) * 16 + lc) * 2;
       const float *s1 = lds + (((h + 2) * NJ + jj) * 16 + lc) * 2;
-      float *dst = GNP + (mtile * 2) * (long)ldY;
+      float *dst = GNP + (gslot * 2) * (long)ldY;
       dst[co] = s0[0] + s1[0];
       dst[ldY + co] = s0[1] + s1[1];
     }
@@ -511,14 +568,60 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> conv3x3_nhwc(
   return a.result();
 }
 
+static torch::Tensor launch_gn_tile_stats(const torch::Tensor &a,
+                                          const torch::Tensor *b,
+                                          torch::Tensor *out);  // ext.hip
+
 // nearest-2x upsample fused into the 3x3 conv (VAE decoder / UNet Upsample
-// blocks): output is [N, Cout, 2H, 2W]; returns (y, partials or None)
+// blocks): output is [N, Cout, 2H, 2W]; returns (y, partials or None).
+// fold (the default route, every shape): four 2x2 sub-pixel convs with the
+// folded weights w_fold = fold_ups2x_weight(w_prep), [4,Cout,2,2,Cin];
+// fold = false keeps the 9-tap kernel (A/B baseline).
 std::tuple<torch::Tensor, c10::optional<torch::Tensor>> ups2x_conv3x3(
     torch::Tensor x, torch::Tensor w_prep, c10::optional<torch::Tensor> bias,
-    bool collect_gn, bool wrap_h = false, bool wrap_w = false) {
+    bool collect_gn, bool wrap_h = false, bool wrap_w = false,
+    c10::optional<torch::Tensor> w_fold = c10::nullopt, bool fold = true) {
+  auto stream = cur_stream();
+  if (fold) {
+    TORCH_CHECK(w_fold.has_value(),
+                "ups2x_conv3x3: fold needs w_fold (fold_ups2x_weight)");
+    const long H = x.size(2), W = x.size(3), Cin = x.size(1);
+    const long Cout = w_prep.size(0), Mp = x.size(0) * H * W;
+    TORCH_CHECK(w_fold->is_cuda() && w_fold->is_contiguous() &&
+                    w_fold->scalar_type() == torch::kBFloat16 &&
+                    w_fold->dim() == 5 && w_fold->size(0) == 4 &&
+                    w_fold->size(1) == Cout && w_fold->size(2) == 2 &&
+                    w_fold->size(3) == 2 && w_fold->size(4) == Cin,
+                "ups2x_conv3x3: w_fold must be bf16 [4,Cout,2,2,Cin]");
+    TORCH_CHECK(Mp < (1L << 31), "ups2x_conv3x3: too many source pixels");
+    TORCH_CHECK(!(wrap_h || wrap_w) || H * W * Cin < (1L << 31),
+                "ups2x_conv3x3: wrapped image too large");
+    // the epilogue serves the partials when every 128-row tile of source
+    // pixels lies in one image; otherwise a stats pass over y follows
+    const bool epi_gn = collect_gn && (H * W) % CONV_BM == 0;
+    ConvArgs a(x, w_prep, bias, c10::nullopt, c10::nullopt, 2 * H, 2 * W,
+               epi_gn);
+    const __hip_bfloat16 *wf = (const __hip_bfloat16 *)w_fold->data_ptr();
+    dispatch_bools(
+        [&](auto B, auto WR) {
+          hipLaunchKernelGGL(
+              (conv3x3_nhwc_bf16_kernel<decltype(B)::value, false, false,
+                                        128, false, decltype(WR)::value,
+                                        true>),
+              conv_grid((a.Cout + CONV_BN - 1) / CONV_BN,
+                        4 * ((Mp + CONV_BM - 1) / CONV_BM)),
+              dim3(256), 0, stream, a.x, wf, a.bias, a.res, a.cb, a.zero,
+              a.yp, a.N, a.H, a.W, a.Cin, a.Cout, a.Ho, a.Wo, 1, a.Cout,
+              a.gnp_ptr, (int)wrap_h, (int)wrap_w);
+        },
+        a.bias != nullptr, wrap_h || wrap_w);
+    if (collect_gn && !epi_gn && ((long)a.Ho * a.Wo) % 128 == 0 &&
+        a.Cout % 8 == 0)  // the stats kernel reads 8-channel vectors
+      a.gnp = launch_gn_tile_stats(a.y, nullptr, nullptr);
+    return a.result();
+  }
   ConvArgs a(x, w_prep, bias, c10::nullopt, c10::nullopt, 2 * x.size(2),
              2 * x.size(3), collect_gn);
-  auto stream = cur_stream();
   dispatch_bools(
       [&](auto B, auto WR) {
         hipLaunchKernelGGL(

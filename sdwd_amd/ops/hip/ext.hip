@@ -534,6 +534,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("wrap_w") = false);
   m.def("ups2x_conv3x3", &ups2x_conv3x3, py::arg("x"), py::arg("w_prep"),
         py::arg("bias"), py::arg("collect_gn"), py::arg("wrap_h") = false,
-        py::arg("wrap_w") = false);
+        py::arg("wrap_w") = false, py::arg("w_fold") = py::none(),
+        py::arg("fold") = true);
   m.def("conv3x3_small_supported", &conv3x3_small_supported);
 }

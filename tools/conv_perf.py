@@ -4,6 +4,10 @@
 --wrap adds, per shape, the wrapped (seamless-tiling) native time next to
 the plain native time, and the time of the library route a tiled conv took
 before the kernels could wrap: F.pad(mode="circular") + F.conv2d.
+
+--ups times only the six fused upsample convs of the headline workload:
+the folded 2x2 sub-pixel kernel against the 9-tap kernel, alternating in
+one process, in ms and in TF/s on the FLOPs each kernel executes.
 """
 import argparse
 import json
@@ -36,6 +40,11 @@ SHAPES = [
 ap = argparse.ArgumentParser(description=__doc__)
 ap.add_argument("--wrap", action="store_true",
                 help="also time wrap=(True, True) and F.pad(circular)+conv2d")
+ap.add_argument("--ups", action="store_true",
+                help="only the fused upsample convs: folded 2x2 sub-pixel "
+                     "kernel vs the 9-tap kernel, alternating in this process")
+ap.add_argument("--rounds", type=int, default=7,
+                help="--ups: alternating rounds per shape")
 args = ap.parse_args()
 
 
@@ -49,6 +58,65 @@ def t(fn, warm=2, it=6):
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / it
 
+
+# (N, Cin, H, W, Cout) of the source image: the three UNet Upsample convs at
+# batch 64 (cond + uncond rows) and the three VAE-decoder ones
+UPS_SHAPES = [
+    (128, 1280, 8, 8, 1280),
+    (128, 1280, 16, 16, 1280),
+    (128, 640, 32, 32, 640),
+    (16, 512, 64, 64, 512),
+    (16, 512, 128, 128, 512),
+    (16, 256, 256, 256, 256),
+]
+
+
+def ups_perf():
+    """Per shape: `rounds` alternating (folded, 9-tap) timings, each of 20
+    calls after 2 warm-up calls. Reports the median, the spread (min..max
+    over the rounds) and the rate on EXECUTED FLOPs: 4 taps x Cin per
+    output for the folded kernel, 9 for the other."""
+    res = {}
+    for (N, Ci, H, W, Co) in UPS_SHAPES:
+        x = torch.randn(N, Ci, H, W, device="cuda", dtype=torch.bfloat16)
+        xc = x.contiguous(memory_format=torch.channels_last)
+        w = torch.randn(Co, Ci, 3, 3, device="cuda",
+                        dtype=torch.bfloat16) * 0.02
+        b = torch.randn(Co, device="cuda", dtype=torch.bfloat16)
+        wp = w.permute(0, 2, 3, 1).contiguous()
+        wf = ops.fold_ups2x_weight(wp)
+        runs = {
+            "fold": lambda: ops.ups2x_conv3x3(xc, wp, b, collect_gn=True,
+                                              w_fold=wf),
+            "tap9": lambda: ops.ups2x_conv3x3(xc, wp, b, collect_gn=True,
+                                              fold=False),
+        }
+        taps = {"fold": 4, "tap9": 9}
+        ts = {k: [] for k in runs}
+        for _ in range(args.rounds):
+            for k, fn in runs.items():
+                ts[k].append(t(fn, warm=2, it=20))
+        row = {}
+        for k, v in ts.items():
+            v = sorted(v)
+            med = v[len(v) // 2]
+            flops = 2 * N * Co * Ci * taps[k] * 4 * H * W
+            row.update({
+                f"{k}_ms": round(med * 1e3, 3),
+                f"{k}_min_ms": round(v[0] * 1e3, 3),
+                f"{k}_max_ms": round(v[-1] * 1e3, 3),
+                f"{k}_tf": round(flops / med / 1e12, 1),
+            })
+        row["speedup"] = round(row["tap9_ms"] / row["fold_ms"], 3)
+        # a gain only if the slowest folded round beats the fastest 9-tap
+        row["clear"] = row["fold_max_ms"] < row["tap9_min_ms"]
+        res[f"{N}x{Ci}x{H}x{W}->{Co}/ups2x"] = row
+    print(json.dumps(res, indent=1))
+
+
+if args.ups:
+    ups_perf()
+    sys.exit(0)
 
 out = {}
 tot_ours = tot_miopen = tot_wrap = tot_padlib = 0.0
