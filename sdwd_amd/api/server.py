@@ -119,6 +119,7 @@ class ServerState:
         # global defaults settable via POST /sdapi/v1/options
         self.default_clip_skip = 1
         self.ensd = 0
+        self.randn_source = "CPU"  # "CPU" | "NV" (pipeline/noise.py)
 
 
 def _b64_png(img: torch.Tensor) -> str:
@@ -610,6 +611,14 @@ def create_app(engine: Optional[LocalEngine] = None,
 
         return HTMLResponse(PAGE)
 
+    def _randn_source(value) -> str:
+        from ..pipeline.noise import normalize_randn_source
+
+        try:
+            return normalize_randn_source(value)
+        except ValueError as exc:
+            raise HTTPException(422, str(exc))
+
     def _overrides(req: Txt2ImgRequest):
         """Per-request override_settings (sdwui convention)."""
         ov = req.override_settings or {}
@@ -623,6 +632,9 @@ def create_app(engine: Optional[LocalEngine] = None,
             or state.default_clip_skip
         )
         ensd = int(ov.get("eta_noise_seed_delta") or state.ensd)
+        randn_source = _randn_source(
+            ov.get("randn_source") or state.randn_source
+        )
         if req.styles:
             from ..pipeline.styles import all_styles, apply_styles, refresh_styles
 
@@ -645,12 +657,12 @@ def create_app(engine: Optional[LocalEngine] = None,
                 refresh_vae_files()
             if vae not in available_vaes():
                 raise HTTPException(404, f"unknown VAE {vae}")
-        return model, clip_skip, ensd, vae
+        return model, clip_skip, ensd, vae, randn_source
 
     @app.post("/sdapi/v1/txt2img")
     def txt2img(req: Txt2ImgRequest):
         control_units = _parse_controlnet(req.alwayson_scripts)
-        model, clip_skip, ensd, vae_ov = _overrides(req)
+        model, clip_skip, ensd, vae_ov, randn_source = _overrides(req)
         gen = GenerationRequest(
             prompt=req.prompt,
             negative_prompt=req.negative_prompt,
@@ -667,6 +679,7 @@ def create_app(engine: Optional[LocalEngine] = None,
             seed_resize_from_w=req.seed_resize_from_w,
             seed_resize_from_h=req.seed_resize_from_h,
             eta_noise_seed_delta=ensd,
+            randn_source=randn_source,
             tiling=req.tiling,
             s_churn=req.s_churn,
             s_tmin=req.s_tmin,
@@ -702,7 +715,7 @@ def create_app(engine: Optional[LocalEngine] = None,
     def img2img(req: Img2ImgRequest):
         if not req.init_images:
             raise HTTPException(422, "init_images required")
-        model, clip_skip, ensd, vae_ov = _overrides(req)
+        model, clip_skip, ensd, vae_ov, randn_source = _overrides(req)
         try:
             inits = torch.stack(
                 [
@@ -740,6 +753,7 @@ def create_app(engine: Optional[LocalEngine] = None,
             seed_resize_from_w=req.seed_resize_from_w,
             seed_resize_from_h=req.seed_resize_from_h,
             eta_noise_seed_delta=ensd,
+            randn_source=randn_source,
             tiling=req.tiling,
             s_churn=req.s_churn,
             s_tmin=req.s_tmin,
@@ -775,6 +789,10 @@ def create_app(engine: Optional[LocalEngine] = None,
             )
         if "eta_noise_seed_delta" in extras:
             state.ensd = int(extras["eta_noise_seed_delta"] or 0)
+        if "randn_source" in extras:
+            state.randn_source = _randn_source(
+                extras["randn_source"] or "CPU"
+            )
         if req.sd_model_checkpoint and req.sd_model_checkpoint != state.current_model:
             name = req.sd_model_checkpoint
             if name not in available_models():
@@ -804,6 +822,7 @@ def create_app(engine: Optional[LocalEngine] = None,
             "sd_vae": getattr(engine, "vae_name", "auto"),
             "CLIP_stop_at_last_layers": state.default_clip_skip,
             "eta_noise_seed_delta": state.ensd,
+            "randn_source": state.randn_source,
         }
 
     @app.get("/sdapi/v1/sd-models")

@@ -431,6 +431,192 @@ def scale(x: torch.Tensor, c: float) -> torch.Tensor:
     return (c * x.float()).to(x.dtype)
 
 
+# ---------------------------------------------------------------------------
+# counter-based noise: Philox4x32-10 + Box-Muller (the "NV" random source)
+# ---------------------------------------------------------------------------
+# Element j of draw `offset` of the generator `seed`:
+#   counter (offset & M32, offset >> 32, j, 0), key (seed & M32, seed >> 32)
+#   (x0, x1, _, _) = philox4x32_10(counter, key)
+#   u = float(x0) * 2^-32 + 2^-33          (fp32, in (0, 1])
+#   v = float(x1) * 2pi*2^-32 + 2pi*2^-33  (fp32, in (0, 2pi])
+#   r = sqrtf(-2 logf(u)) * sinf(v)
+# One normal per counter, by definition of that source (docs/usage.md).
+_M32 = 0xFFFFFFFF
+_PHILOX_M0 = 0xD2511F53
+_PHILOX_M1 = 0xCD9E8D57
+_PHILOX_W0 = 0x9E3779B9
+_PHILOX_W1 = 0xBB67AE85
+_TWO_PI = 2.0 * math.pi
+
+
+def _mulhilo32(m: int, c: torch.Tensor):
+    """(hi, lo) words of m*c for a 32-bit constant m and int64 c < 2^32,
+    without leaving int64: c is split into 16-bit halves."""
+    a = m * (c & 0xFFFF)           # < 2^48
+    b = m * (c >> 16)              # < 2^48
+    hi = ((a >> 16) + b) >> 16
+    lo = (a + ((b & 0xFFFF) << 16)) & _M32
+    return hi, lo
+
+
+def _philox_rounds(c0, c1, c2, c3, k0, k1):
+    for _ in range(10):
+        h0, l0 = _mulhilo32(_PHILOX_M0, c0)
+        h1, l1 = _mulhilo32(_PHILOX_M1, c2)
+        c0, c1, c2, c3 = h1 ^ c1 ^ k0, l1, h0 ^ c3 ^ k1, l0
+        k0 = (k0 + _PHILOX_W0) & _M32
+        k1 = (k1 + _PHILOX_W1) & _M32
+    return c0, c1, c2, c3
+
+
+def _uint32_table(name: str, t, cols: int) -> torch.Tensor:
+    t = torch.as_tensor(t)
+    if t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError(f"philox4x32: {name} must be an int64 [N, {cols}]")
+    return t
+
+
+def philox4x32(counter: torch.Tensor, key: torch.Tensor) -> torch.Tensor:
+    """Philox4x32-10 at raw counters [N,4] and keys [N,2] -> words [N,4];
+    int64 tensors that hold uint32 values. Exists so the core can be pinned
+    bit for bit; GPU: philox4x32_kernel (ops/hip/rng.hip), CPU: int64 torch
+    ops."""
+    counter = _uint32_table("counter", counter, 4)
+    key = _uint32_table("key", key, 2)
+    if counter.shape[0] != key.shape[0] or counter.device != key.device:
+        raise ValueError("philox4x32: counter and key must pair up, [N,4]/[N,2]")
+    if counter.is_cuda:
+        return ext().philox4x32(counter.contiguous(), key.contiguous())
+    c = counter & _M32
+    k = key & _M32
+    return torch.stack(
+        _philox_rounds(c[:, 0], c[:, 1], c[:, 2], c[:, 3], k[:, 0], k[:, 1]),
+        dim=1,
+    )
+
+
+def _philox_seeds(seeds, device) -> torch.Tensor:
+    """Per-image generator seeds as an int64 [B] table on `device` (the bit
+    pattern of the uint64 seed). A device int64 tensor is taken as it is so
+    a caller can upload it once; host seeds are validated here."""
+    device = torch.device(device)
+    if torch.is_tensor(seeds) and seeds.device.type != "cpu":
+        if seeds.dtype != torch.int64 or seeds.dim() != 1:
+            raise ValueError("philox: a device `seeds` must be an int64 [B]")
+        if seeds.device != device:
+            raise ValueError(
+                f"philox: seeds is on {seeds.device}, expected {device}"
+            )
+        return seeds.contiguous()
+    if torch.is_tensor(seeds):
+        if seeds.dtype.is_floating_point or seeds.dtype == torch.bool \
+                or seeds.dim() != 1:
+            raise ValueError("philox: seeds must be a 1-d table of integers")
+        vals = seeds.tolist()
+    else:
+        vals = list(seeds)
+    out = []
+    for s in vals:
+        if isinstance(s, bool) or not isinstance(s, int):
+            raise ValueError(f"philox: seeds must be integers (got {s!r})")
+        if not 0 <= s < (1 << 64):
+            raise ValueError(
+                f"philox: seeds must lie in [0, 2^64) (got {s})"
+            )
+        out.append(s - (1 << 64) if s >= (1 << 63) else s)
+    return torch.tensor(out, dtype=torch.int64).to(device)
+
+
+def _philox_offset(offset) -> int:
+    if isinstance(offset, bool) or not isinstance(offset, int) \
+            or not 0 <= offset < (1 << 64):
+        raise ValueError(
+            f"philox: offset must be an integer in [0, 2^64) (got {offset!r})"
+        )
+    return offset
+
+
+def _philox_normals_cpu(seeds: torch.Tensor, offset: int, n: int):
+    """fp32 normals [B, n] from an int64 [B] seed table."""
+    j = torch.arange(n, dtype=torch.int64)[None, :]
+    zero = torch.zeros_like(j)
+    k0 = (seeds & _M32)[:, None]
+    k1 = ((seeds >> 32) & _M32)[:, None]
+    x0, x1, _, _ = _philox_rounds(
+        zero + (offset & _M32), zero + (offset >> 32), j, zero,
+        k0.expand(-1, n), k1.expand(-1, n),
+    )
+    u = x0.to(torch.float32) * (2.0 ** -32) + (2.0 ** -33)
+    v = x1.to(torch.float32) * (_TWO_PI * 2.0 ** -32) + (_TWO_PI * 2.0 ** -33)
+    return torch.sqrt(-2.0 * torch.log(u)) * torch.sin(v)
+
+
+def philox_randn(
+    seeds, offset: int, shape, dtype=torch.float32, device="cpu"
+) -> torch.Tensor:
+    """[B, *shape] normals: row b is draw `offset` of the generator
+    seeds[b]; element j (C-order within `shape`) depends on (seed, offset,
+    j) alone, so it is the same on every device, shard and batch position.
+
+    seeds: a list or CPU tensor of integers in [0, 2^64), or a device int64
+    tensor (two's-complement bit pattern) taken as it is. GPU:
+    philox_randn_kernel; CPU: the same definition in torch int64/fp32 ops
+    (the numerics oracle)."""
+    device = torch.device(device)
+    sd = _philox_seeds(seeds, device)
+    offset = _philox_offset(offset)
+    shape = tuple(int(s) for s in shape)
+    n = int(math.prod(shape))
+    if not 0 <= n < (1 << 32):
+        raise ValueError("philox_randn: a draw holds fewer than 2^32 elements")
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("philox_randn: dtype must be float32 or bfloat16")
+    b = sd.shape[0]
+    if device.type == "cuda":
+        out = ext().philox_randn(
+            sd, offset & _M32, offset >> 32, n, dtype == torch.bfloat16
+        )
+    else:
+        out = _philox_normals_cpu(sd, offset, n).to(dtype)
+    return out.reshape(b, *shape)
+
+
+def add_philox_noise(
+    x: torch.Tensor, seeds, offset: int, a: float, b: float
+) -> torch.Tensor:
+    """a*x + b*philox_randn(seeds, offset, x.shape[1:]) in fp32 math, without
+    materialising the noise on the GPU (axpby_philox_kernel, one launch).
+    x: [B, C, H, W], fp32 or bf16, contiguous or channels_last (the result
+    keeps that format; any other layout is made contiguous first). The noise
+    index is the logical (c, h, w) position whatever the memory format."""
+    if x.dim() != 4:
+        raise ValueError("add_philox_noise: x must be [B, C, H, W]")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("add_philox_noise: x must be float32 or bfloat16")
+    sd = _philox_seeds(seeds, x.device)
+    offset = _philox_offset(offset)
+    if sd.shape[0] != x.shape[0]:
+        raise ValueError(
+            f"add_philox_noise: {sd.shape[0]} seeds for a batch of "
+            f"{x.shape[0]}"
+        )
+    if not (x.is_contiguous()
+            or x.is_contiguous(memory_format=torch.channels_last)):
+        x = x.contiguous()
+    if x.is_cuda:
+        return ext().axpby_philox(
+            x, sd, offset & _M32, offset >> 32, float(a), float(b)
+        )
+    n = x[0].numel()
+    if n >= (1 << 32):
+        raise ValueError("add_philox_noise: an image holds fewer than 2^32 "
+                         "elements")
+    r = _philox_normals_cpu(sd, offset, n).reshape(x.shape)
+    out = torch.empty_like(x)  # keeps x's memory format
+    out.copy_(float(a) * x.float() + float(b) * r)
+    return out
+
+
 def _attach_gn_partials(
     y: torch.Tensor, gnp: Optional[torch.Tensor]
 ) -> None:

@@ -18,6 +18,7 @@ static inline hipStream_t cur_stream() {
 #include "conv_v4.hip"
 #include "conv.hip"
 #include "conv_small.hip"
+#include "rng.hip"
 
 #define CHECK_IN(x)                                                     \
   TORCH_CHECK(x.is_cuda(), #x " must be on GPU");                        \
@@ -496,11 +497,130 @@ torch::Tensor attention_blend_bshd(torch::Tensor q, torch::Tensor k,
   return flash_blend_raw(q, k, v, w, kv_index, kv_len, scale);
 }
 
+// ---------------------------------------------------------------------------
+// counter-based noise (rng.hip): Philox4x32-10 + Box-Muller
+// ---------------------------------------------------------------------------
+torch::Tensor philox4x32(torch::Tensor counter, torch::Tensor key) {
+  CHECK_IN(counter);
+  CHECK_IN(key);
+  TORCH_CHECK(counter.scalar_type() == torch::kLong &&
+                  key.scalar_type() == torch::kLong && counter.dim() == 2 &&
+                  key.dim() == 2 && counter.size(1) == 4 &&
+                  key.size(1) == 2 && counter.size(0) == key.size(0),
+              "philox4x32: int64 counter [N,4] and key [N,2]");
+  auto out = torch::empty_like(counter);
+  const long n = counter.size(0);
+  if (n == 0) return out;
+  hipLaunchKernelGGL(philox4x32_kernel, dim3(ew_grid(n)), dim3(256), 0,
+                     cur_stream(), (const long long *)counter.data_ptr(),
+                     (const long long *)key.data_ptr(),
+                     (long long *)out.data_ptr(), n);
+  return out;
+}
+
+static void check_philox_seeds(const torch::Tensor &seeds, long B,
+                               const torch::Tensor *like) {
+  TORCH_CHECK(seeds.is_cuda() && seeds.scalar_type() == torch::kLong &&
+                  seeds.dim() == 1 && seeds.is_contiguous() &&
+                  seeds.size(0) == B,
+              "philox: seeds must be a contiguous int64 [B] on the GPU");
+  TORCH_CHECK(!like || seeds.device() == like->device(),
+              "philox: seeds and x must share a device");
+}
+
+static void check_philox_offset(long off_lo, long off_hi) {
+  TORCH_CHECK(off_lo >= 0 && off_lo <= 0xFFFFFFFFL && off_hi >= 0 &&
+                  off_hi <= 0xFFFFFFFFL,
+              "philox: the offset halves are 32-bit words");
+}
+
+// [B, n] normals; row b is draw (off_hi:off_lo) of the generator seeds[b]
+torch::Tensor philox_randn(torch::Tensor seeds, long off_lo, long off_hi,
+                           long n, bool bf16) {
+  TORCH_CHECK(seeds.dim() == 1, "philox_randn: seeds must be [B]");
+  const long B = seeds.size(0);
+  check_philox_seeds(seeds, B, nullptr);
+  check_philox_offset(off_lo, off_hi);
+  TORCH_CHECK(n >= 0 && n < (1L << 32), "philox_randn: n must be < 2^32");
+  auto out = torch::empty(
+      {B, n}, seeds.options().dtype(bf16 ? torch::kBFloat16 : torch::kFloat));
+  const long total = B * n;
+  if (total == 0) return out;
+  if (bf16) {
+    const long nv = total / 8;
+    hipLaunchKernelGGL(philox_randn_kernel<__hip_bfloat16>,
+                       dim3(ew_grid(nv ? nv : total)), dim3(256), 0,
+                       cur_stream(), (const long long *)seeds.data_ptr(),
+                       (__hip_bfloat16 *)out.data_ptr(), (unsigned)off_lo,
+                       (unsigned)off_hi, (unsigned)n, nv, total);
+  } else {
+    const long nv = total / 4;
+    hipLaunchKernelGGL(philox_randn_kernel<float>,
+                       dim3(ew_grid(nv ? nv : total)), dim3(256), 0,
+                       cur_stream(), (const long long *)seeds.data_ptr(),
+                       out.data_ptr<float>(), (unsigned)off_lo,
+                       (unsigned)off_hi, (unsigned)n, nv, total);
+  }
+  return out;
+}
+
+// a*x + b*randn(seeds[img], offset, j) for x [B,C,H,W], contiguous or
+// channels_last; the result keeps x's memory format
+torch::Tensor axpby_philox(torch::Tensor x, torch::Tensor seeds, long off_lo,
+                           long off_hi, double a, double b) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4, "axpby_philox: x must be a GPU "
+                                           "[B,C,H,W] tensor");
+  const bool cl = !x.is_contiguous() &&
+                  x.is_contiguous(torch::MemoryFormat::ChannelsLast);
+  TORCH_CHECK(x.is_contiguous() || cl,
+              "axpby_philox: x must be contiguous or channels_last");
+  const long B = x.size(0), C = x.size(1);
+  const long HW = x.size(2) * (long)x.size(3);
+  const long n = C * HW;
+  check_philox_seeds(seeds, B, &x);
+  check_philox_offset(off_lo, off_hi);
+  TORCH_CHECK(n < (1L << 32), "axpby_philox: C*H*W must be < 2^32");
+  auto out = torch::empty_like(x);  // keeps x's strides
+  const long total = B * n;
+  if (total == 0) return out;
+  // a view at an odd storage offset is re-materialised for the 16 B loads
+  if (reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 != 0) x = x.clone();
+  auto launch = [&](auto kern, auto *xp, auto *op, long vec) {
+    const long nv = total / vec;
+    hipLaunchKernelGGL(kern, dim3(ew_grid(nv ? nv : total)), dim3(256), 0,
+                       cur_stream(), xp, (const long long *)seeds.data_ptr(),
+                       op, (float)a, (float)b, (unsigned)off_lo,
+                       (unsigned)off_hi, (unsigned)n, (unsigned)C,
+                       (unsigned)HW, nv, total);
+  };
+  if (x.scalar_type() == torch::kBFloat16) {
+    auto *xp = (const __hip_bfloat16 *)x.data_ptr();
+    auto *op = (__hip_bfloat16 *)out.data_ptr();
+    if (cl)
+      launch(axpby_philox_kernel<__hip_bfloat16, true>, xp, op, 8);
+    else
+      launch(axpby_philox_kernel<__hip_bfloat16, false>, xp, op, 8);
+  } else if (x.scalar_type() == torch::kFloat) {
+    auto *xp = (const float *)x.data_ptr();
+    auto *op = (float *)out.data_ptr();
+    if (cl)
+      launch(axpby_philox_kernel<float, true>, xp, op, 4);
+    else
+      launch(axpby_philox_kernel<float, false>, xp, op, 4);
+  } else {
+    TORCH_CHECK(false, "axpby_philox: unsupported dtype");
+  }
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("silu", &silu);
   m.def("geglu", &geglu);
   m.def("axpby", &axpby);
   m.def("euler_step", &euler_step);
+  m.def("philox4x32", &philox4x32);
+  m.def("philox_randn", &philox_randn);
+  m.def("axpby_philox", &axpby_philox);
   m.def("group_norm_silu", &group_norm_silu);
   m.def("group_norm_silu_pre", &group_norm_silu_pre);
   m.def("gn_tile_stats", &gn_tile_stats);

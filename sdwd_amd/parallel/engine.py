@@ -25,6 +25,7 @@ import torch
 
 from ..core import GenRequest, Job, State, World, Worker
 from ..pipeline import PipelineRequest, StableDiffusionPipeline
+from ..pipeline.noise import normalize_randn_source
 from ..pipeline.pipeline import hires_active, hr_target_resolution
 from ..utils import get_logger
 from ..utils.images import make_grid
@@ -72,6 +73,7 @@ class GenerationRequest:
     seed_resize_from_w: int = 0
     seed_resize_from_h: int = 0
     eta_noise_seed_delta: int = 0
+    randn_source: str = "CPU"  # "CPU" | "NV" (pipeline/noise.py)
     init_images: Optional[torch.Tensor] = None  # [B,H,W,3] uint8 (img2img)
     denoising_strength: float = 0.75
     mask_image: Optional[torch.Tensor] = None   # [H,W] uint8, 255=repaint
@@ -124,6 +126,9 @@ class GenerationRequest:
     si_mask_influence: float = 0.0
     si_difference_threshold: float = 0.5
     si_difference_contrast: float = 2.0
+
+    def __post_init__(self) -> None:
+        self.randn_source = normalize_randn_source(self.randn_source)
 
     def sched(self) -> GenRequest:
         hr_on = hires_active(
@@ -190,6 +195,7 @@ def _job_pipeline_request(
         seed_resize_from_w=gen.seed_resize_from_w,
         seed_resize_from_h=gen.seed_resize_from_h,
         eta_noise_seed_delta=gen.eta_noise_seed_delta,
+        randn_source=gen.randn_source,
         init_latents=init_latents,
         denoising_strength=gen.denoising_strength,
         mask_image=gen.mask_image,
@@ -630,7 +636,9 @@ class LocalEngine(_EngineBase):
                     (job.gallery_offset + i) % src.shape[0]
                     for i in range(job.batch_size)
                 ]
-                init_latents = pipe.encode_image(src[idx], seeds=job.seeds)
+                init_latents = pipe.encode_image(
+                    src[idx], seeds=job.seeds, randn_source=gen.randn_source
+                )
             t0 = time.perf_counter()
 
             def on_step(i, n, _job=job):
@@ -963,7 +971,7 @@ class DistributedEngine(_EngineBase):
                     for i in range(job.batch_size)
                 ]
                 init_latents = self.pipe.encode_image(
-                    src[idx], seeds=job.seeds
+                    src[idx], seeds=job.seeds, randn_source=gen.randn_source
                 )
             ts = time.perf_counter()
 
@@ -1007,10 +1015,16 @@ class DistributedEngine(_EngineBase):
         self.heartbeat()
         self._clear_interrupt()
         if self.rank == 0:
-            plan = (gen.model, self.world.make_jobs(gen.sched()))
+            plan = (
+                gen.model, self.world.make_jobs(gen.sched()),
+                gen.randn_source,
+            )
         else:
             plan = None
-        model_name, jobs = pg.broadcast_object(plan)
+        model_name, jobs, randn_source = pg.broadcast_object(plan)
+        if randn_source != gen.randn_source:
+            # the noise source decides every image: rank 0's choice holds
+            gen = replace_dc(gen, randn_source=randn_source)
         self.set_model(model_name)
         # per-worker checkpoint override (ref ui.py:161-171): purely local —
         # no collective weight sync, the deterministic registry (or the

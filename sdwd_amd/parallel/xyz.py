@@ -163,6 +163,9 @@ AXIS_OPTIONS: List[AxisOption] = [
     AxisOption("Eta", "float", lambda g, v: replace(g, eta=float(v))),
     AxisOption("Width", "int", lambda g, v: replace(g, width=int(v))),
     AxisOption("Height", "int", lambda g, v: replace(g, height=int(v))),
+    AxisOption(
+        "RNG source", "str", lambda g, v: replace(g, randn_source=str(v))
+    ),
 ]
 
 _BY_NAME = {o.name.lower(): i for i, o in enumerate(AXIS_OPTIONS)}
@@ -177,6 +180,7 @@ _BY_NAME.update({
     "clip_skip": 10, "denoising strength": 11,
     "schedule": 14, "scheduler": 14,
     "eta noise seed delta": 19,
+    "rng": 23, "randn_source": 23, "random number generator source": 23,
 })
 
 

@@ -4,8 +4,9 @@ POST /txt2img|/img2img runs here, in-process.
 Determinism contract (ref C22): image k of a batch depends only on
 (model, seed_k, subseed_k, request params) — never on batch position,
 shard size or device count — so an 8-GPU gallery is image-for-image equal
-to the 1-GPU gallery. Initial noise is drawn per-image from a CPU
-generator seeded with that image's seed, then moved to the device.
+to the 1-GPU gallery. All noise comes from the request's noise source
+(noise.py): per-image CPU generators seeded with that image's seed by
+default, or the counter-based device stream keyed by it (randn_source "NV").
 """
 from __future__ import annotations
 
@@ -21,6 +22,9 @@ from ..models.registry import ModelBundle, load_model
 from ..models import tokenizer
 from ..utils import get_logger
 from .graphs import GraphedDenoiser, GraphedModelFn, graphs_enabled
+from .noise import (  # noqa: F401 - _image_noise/_slerp re-exported
+    KEY_ENCODE, _image_noise, _slerp, keyed_noise, make_noise_source,
+)
 from .samplers import build_sampler
 from .schedule import schedule_for, sigma_for_t
 
@@ -50,6 +54,9 @@ class PipelineRequest:
     seed_resize_from_h: int = 0
     # sdwui eta_noise_seed_delta: offsets the ancestral-noise seeds
     eta_noise_seed_delta: int = 0
+    # sdwui "Random number generator source": "CPU" (per-image host
+    # generators) or "NV" (the device-side Philox stream, pipeline/noise.py)
+    randn_source: str = "CPU"
     # img2img
     init_latents: Optional[torch.Tensor] = None  # pre-encoded [B,4,h,w]
     denoising_strength: float = 0.75
@@ -131,21 +138,6 @@ class PipelineResult:
     infotexts: List[str]
     elapsed: float = 0.0
     interrupted: bool = False
-
-
-def _slerp(a: torch.Tensor, b: torch.Tensor, t: float) -> torch.Tensor:
-    """Spherical interpolation between noise tensors (subseed variation)."""
-    af, bf = a.flatten().double(), b.flatten().double()
-    dot = torch.dot(af / af.norm(), bf / bf.norm()).clamp(-1, 1)
-    omega = torch.acos(dot)
-    if omega.abs() < 1e-6:
-        out = (1 - t) * af + t * bf
-    else:
-        so = torch.sin(omega)
-        out = (math.sin((1 - t) * omega) / so) * af + (
-            math.sin(t * omega) / so
-        ) * bf
-    return out.reshape(a.shape).to(a.dtype)
 
 
 def _parse_regional(req: "PipelineRequest"):
@@ -315,22 +307,6 @@ def _apply_sampler_params(sampler, req: "PipelineRequest") -> None:
     sampler.s_noise = float(req.s_noise)
     if req.eta >= 0:  # sdwui Eta; -1 keeps the sampler's own default
         sampler.eta = float(req.eta)
-
-
-def _image_noise(
-    seed: int,
-    subseed: int,
-    subseed_strength: float,
-    shape,
-) -> torch.Tensor:
-    """Per-image deterministic CPU noise (device-independent)."""
-    g = torch.Generator("cpu").manual_seed(int(seed) & 0xFFFFFFFF)
-    noise = torch.randn(shape, generator=g, dtype=torch.float32)
-    if subseed_strength and subseed_strength > 0 and subseed >= 0:
-        g2 = torch.Generator("cpu").manual_seed(int(subseed) & 0xFFFFFFFF)
-        noise2 = torch.randn(shape, generator=g2, dtype=torch.float32)
-        noise = _slerp(noise, noise2, float(subseed_strength))
-    return noise
 
 
 class StableDiffusionPipeline:
@@ -581,6 +557,7 @@ class StableDiffusionPipeline:
         lat = self.encode_image(
             torch.stack(outs),
             seeds=[(int(s) ^ 0x9C51) & 0xFFFFFFFF for s in req.seeds],
+            randn_source=req.randn_source,
         )
         return lat.to(self.dtype)
 
@@ -712,15 +689,11 @@ class StableDiffusionPipeline:
             noise_shape = (
                 lat_c, req.seed_resize_from_h // f, req.seed_resize_from_w // f
             )
-        noise = torch.stack(
-            [
-                _image_noise(
-                    req.seeds[i], subseeds[i], req.subseed_strength,
-                    noise_shape,
-                )
-                for i in range(b)
-            ]
+        source = make_noise_source(
+            req.randn_source, req.seeds, subseeds, req.subseed_strength,
+            req.eta_noise_seed_delta, self.device, self.dtype,
         )
+        noise = source.initial(noise_shape)
         if noise_shape != (lat_c, lat_h, lat_w):
             noise = torch.nn.functional.interpolate(
                 noise, size=(lat_h, lat_w), mode="bilinear",
@@ -746,16 +719,7 @@ class StableDiffusionPipeline:
                     req.mask_image, b, lat_h, lat_w
                 )
                 if req.inpainting_fill == 2:  # latent noise
-                    content = torch.stack([
-                        torch.randn(
-                            (lat_c, lat_h, lat_w),
-                            generator=torch.Generator("cpu").manual_seed(
-                                (int(sd) ^ 0xF111) & 0xFFFFFFFF
-                            ),
-                            dtype=torch.float32,
-                        )
-                        for sd in req.seeds
-                    ]).to(self.device)
+                    content = source.fill((lat_c, lat_h, lat_w))
                 else:  # latent nothing
                     content = torch.zeros_like(init_lat0)
                 init_lat0 = (1.0 - lm) * init_lat0 + lm * content
@@ -763,26 +727,10 @@ class StableDiffusionPipeline:
         else:
             x = (noise.float() * float(sig[0])).to(self.dtype)
 
-        # ancestral noise: per-image generators stepped identically regardless
-        # of shard composition
-        ensd = int(req.eta_noise_seed_delta)
-        gens = [
-            torch.Generator("cpu").manual_seed(
-                ((int(s) + ensd) ^ 0x5EED) & 0xFFFFFFFF
-            )
-            for s in req.seeds
-        ]
-
-        def noise_fn() -> torch.Tensor:
-            n = torch.stack(
-                [
-                    torch.randn(
-                        (lat_c, lat_h, lat_w), generator=g, dtype=torch.float32
-                    )
-                    for g in gens
-                ]
-            )
-            return n.to(self.device, self.dtype)
+        # ancestral noise: the source steps every image's stream identically
+        # regardless of shard composition
+        source.shape = (lat_c, lat_h, lat_w)
+        noise_fn = source
 
         cfg = float(req.cfg_scale)
         unet = self.model.unet
@@ -1272,30 +1220,13 @@ class StableDiffusionPipeline:
             hsampler = build_sampler(hr_sampler, hsched)
             _apply_sampler_params(hsampler, req)
             hh, hw = x.shape[2], x.shape[3]
-            hr_noise = torch.stack(
-                [
-                    _image_noise(
-                        (int(req.seeds[i]) ^ 0x12E50),
-                        subseeds[i],
-                        0.0,
-                        (lat_c, hh, hw),
-                    )
-                    for i in range(b)
-                ]
-            ).to(self.device, self.dtype)
+            hr_noise = source.hires_initial((lat_c, hh, hw)).to(
+                self.device, self.dtype
+            )
             s0 = float(hsched.sigmas[0])
             x = (x.float() + hr_noise.float() * s0).to(self.dtype)
 
-            def hr_noise_fn() -> torch.Tensor:
-                n = torch.stack(
-                    [
-                        torch.randn(
-                            (lat_c, hh, hw), generator=g, dtype=torch.float32
-                        )
-                        for g in gens
-                    ]
-                )
-                return n.to(self.device, self.dtype)
+            source.shape = (lat_c, hh, hw)
 
             def hr_post(xc, sigma_next):
                 # live preview only (the inpainting re-imposition, if any,
@@ -1304,7 +1235,7 @@ class StableDiffusionPipeline:
                 return xc
 
             x = hsampler.sample(
-                model_fn, x, noise_fn=hr_noise_fn, callback=step_callback,
+                model_fn, x, noise_fn=source, callback=step_callback,
                 interrupt=_interrupt, post_step=hr_post,
             )
 
@@ -1363,6 +1294,10 @@ class StableDiffusionPipeline:
             extra += f", Variation seed strength: {req.subseed_strength}"
         if req.eta >= 0:
             extra += f", Eta: {req.eta}"
+        if req.eta_noise_seed_delta != 0:
+            extra += f", ENSD: {int(req.eta_noise_seed_delta)}"
+        if source.randn_source == "NV":
+            extra += ", RNG: NV"
         if hires_active(
             req.enable_hr, req.hr_scale, req.hr_resize_x, req.hr_resize_y
         ):
@@ -1431,7 +1366,8 @@ class StableDiffusionPipeline:
 
     @torch.no_grad()
     def encode_image(
-        self, images: torch.Tensor, seeds: Optional[List[int]] = None
+        self, images: torch.Tensor, seeds: Optional[List[int]] = None,
+        randn_source: str = "CPU",
     ) -> torch.Tensor:
         """[B,H,W,3] uint8 -> latents [B,4,h,w] (img2img entry).
 
@@ -1455,13 +1391,10 @@ class StableDiffusionPipeline:
                 moments = self.model.vae.encoder(x[i : i + 1])
                 mean, logvar = moments.chunk(2, dim=1)
                 std = torch.exp(0.5 * logvar.float().clamp(-30, 20))
-                noise = torch.randn(
-                    mean.shape[1:],
-                    generator=torch.Generator("cpu").manual_seed(
-                        (int(sd) ^ 0xE4C0DE) & 0xFFFFFFFF
-                    ),
-                    dtype=torch.float32,
-                )[None].to(self.device)
+                noise = keyed_noise(
+                    randn_source, [sd], KEY_ENCODE, mean.shape[1:],
+                    self.device,
+                )
                 lats.append(
                     (mean.float() + std * noise)
                     * self.model.vae.cfg.scale_factor

@@ -37,6 +37,16 @@ def _eval(model_fn: ModelFn, x: torch.Tensor, sigma: float, t: float):
     return _denoised(x, eps, sigma)
 
 
+def _noised(x: torch.Tensor, noise_fn, amp: float) -> torch.Tensor:
+    """x + amp * (the next draw of noise_fn). A noise source with add_to
+    (pipeline/noise.py) fuses the draw into the update; a plain callable
+    returning the noise tensor works as before."""
+    add_to = getattr(noise_fn, "add_to", None)
+    if add_to is not None:
+        return add_to(x, 1.0, amp)
+    return ops.add_noise(x, noise_fn(), 1.0, amp)
+
+
 def _ancestral_sigmas(sigma: float, sigma_next: float, eta: float = 1.0):
     if sigma_next <= 0:
         return 0.0, 0.0
@@ -80,7 +90,7 @@ class Sampler:
         sigma_hat = sigma * (1 + gamma)
         if noise_fn is not None and sigma_hat > sigma:
             extra = (sigma_hat ** 2 - sigma ** 2) ** 0.5 * self.s_noise
-            x = ops.add_noise(x, noise_fn(), 1.0, extra)
+            x = _noised(x, noise_fn, extra)
         return x, sigma_hat
 
     def sample(
@@ -147,7 +157,7 @@ class EulerAncestral(Sampler):
         sd, su = _ancestral_sigmas(sigma, sigma_next, self.eta)
         x = ops.euler_step(x, denoised, sigma, sd)
         if su > 0 and noise_fn is not None:
-            x = ops.add_noise(x, noise_fn(), 1.0, su)
+            x = _noised(x, noise_fn, su)
         return x
 
 
@@ -221,7 +231,7 @@ class DPMppSDE(Sampler):
         sd, su = _ancestral_sigmas(sigma, sigma_next, self.eta)
         x = ops.euler_step(x, denoised2, sigma, sd)
         if su > 0 and noise_fn is not None:
-            x = ops.add_noise(x, noise_fn(), 1.0, su)
+            x = _noised(x, noise_fn, su)
         return x
 
 
@@ -253,7 +263,7 @@ class DPMpp2MSDE(Sampler):
             x = ops.lincomb(x, d, 1.0, self._ms_coeff(phi, h, eta_h) / r)
         if self.eta > 0 and noise_fn is not None:
             amp = sigma_next * math.sqrt(max(0.0, -math.expm1(-2 * eta_h)))
-            x = ops.add_noise(x, noise_fn(), 1.0, amp)
+            x = _noised(x, noise_fn, amp)
         self.old_denoised = denoised
         self.h_last = h
         return x
@@ -324,7 +334,7 @@ class DPMpp3MSDE(Sampler):
             amp = sigma_next * math.sqrt(
                 max(0.0, -math.expm1(-2 * h * self.eta))
             )
-            x = ops.add_noise(x, noise_fn(), 1.0, amp)
+            x = _noised(x, noise_fn, amp)
         self.den_2 = self.den_1
         self.den_1 = denoised
         self.h_2 = self.h_1
@@ -353,7 +363,7 @@ class DPM2(Sampler):
         d2 = ops.lincomb(x_mid, denoised2, 1.0 / sigma_mid, -1.0 / sigma_mid)
         x = ops.lincomb(x, d2, 1.0, sd - sigma)
         if su > 0 and noise_fn is not None:
-            x = ops.add_noise(x, noise_fn(), 1.0, su)
+            x = _noised(x, noise_fn, su)
         return x
 
 
@@ -384,7 +394,7 @@ class DPMpp2SAncestral(Sampler):
         denoised2 = _eval(model_fn, x2, sig_s, t_mid)
         x = ops.lincomb(x, denoised2, sd / sigma, -math.expm1(-h))
         if su > 0 and noise_fn is not None:
-            x = ops.add_noise(x, noise_fn(), 1.0, su)
+            x = _noised(x, noise_fn, su)
         return x
 
 
@@ -526,7 +536,7 @@ class Restart(Sampler):
             s_hi, s_lo = sig[a], sig[bi]
             for _ in range(restarts):
                 bump = math.sqrt(max(0.0, s_hi * s_hi - s_lo * s_lo))
-                x = ops.add_noise(x, noise_fn(), 1.0, bump)
+                x = _noised(x, noise_fn, bump)
                 x, stop = descend(x, a, bi)
                 if stop:
                     break
@@ -544,7 +554,7 @@ class LCM(Sampler):
         denoised = _eval(model_fn, x, sigma, t)
         if sigma_next <= 0 or noise_fn is None:
             return denoised
-        return ops.add_noise(denoised, noise_fn(), 1.0, sigma_next)
+        return _noised(denoised, noise_fn, sigma_next)
 
 
 class _DPMSolver(Sampler):

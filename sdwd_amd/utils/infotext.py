@@ -18,6 +18,10 @@ _RE_PARAM = re.compile(
 )
 
 
+# infotext key -> request field it restores
+_REQUEST_FIELDS = {"RNG": "randn_source", "ENSD": "eta_noise_seed_delta"}
+
+
 def _unquote(v: str) -> str:
     v = v.strip()
     if len(v) >= 2 and v[0] == '"' and v[-1] == '"':
@@ -30,7 +34,10 @@ def parse_infotext(text: str) -> Dict[str, str]:
 
     Returns at least ``prompt`` and ``negative_prompt`` (possibly empty)
     plus one entry per ``Key: value`` pair from the final parameter line,
-    keys as written ("Steps", "CFG scale", "Worker Label", ...).
+    keys as written ("Steps", "CFG scale", "Worker Label", ...). The two
+    settings an image cannot be reproduced without are also returned under
+    their request field names: ``RNG`` as ``randn_source`` and ``ENSD`` as
+    ``eta_noise_seed_delta``.
     """
     lines = (text or "").split("\n")
     # the parameter line is the LAST line iff it parses as k:v pairs
@@ -59,4 +66,7 @@ def parse_infotext(text: str) -> Dict[str, str]:
         key = m.group("key").strip()
         if key:
             out[key] = _unquote(m.group("val"))
+    for key, name in _REQUEST_FIELDS.items():
+        if key in out:
+            out[name] = out[key]
     return out
