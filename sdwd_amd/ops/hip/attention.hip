@@ -1,24 +1,53 @@
 // Flash-style fused attention forward for gfx950 (MFMA 32x32x16 bf16).
 //
-// Structure (v2):
-//  * workgroup = 4 waves; each wave owns 32 q-rows, the WG shares K/V tiles
-//    of 32 keys staged in LDS (K row-major padded, V transposed for
-//    contiguous B-fragment reads).
+// Three kernels built from one set of pieces.
+//
+// Shared by all three (the helpers below, each written once):
+//  * workgroup = 4 waves; each wave owns QS 32-row q-subtiles, the WG shares
+//    K/V tiles of KVB = 64 keys staged in LDS (AttnGeom<DPAD>).
 //  * swapped QK^T: S^T = mfma(K_frag, Q_frag) so each lane holds the scores
-//    of ONE q-row (lane%32) across 16 of 32 keys — softmax is register-local
-//    plus one __shfl_xor(32) to combine the half-wave pair.
+//    of ONE q-row (lane%32) across 16 of 32 keys (crow() names the row of
+//    an accumulator register) — softmax is register-local plus one
+//    __shfl_xor(32) to combine the half-wave pair. Q fragments are read once
+//    (load_q_frags).
 //  * P (bf16-packed) is redistributed to the PV A-fragment layout with
-//    v_permlane32_swap pairs (guide T12), then PV accumulates fp32 via MFMA.
-//  * online softmax with per-tile rescale; the previous tile's PV completes
-//    before the rescale decision (textbook order).
+//    v_permlane32_swap pairs (guide T12, p_relayout), then PV accumulates
+//    fp32 via MFMA.
+//  * per-row factors (the online-softmax rescale, 1/l, w/l) live in the lane
+//    that owns the row and reach accumulator register r by
+//    __shfl(f, crow(r, half)).
 //  * STRIDED access: Q/K/V/O are addressed with (batch, head, row) strides,
 //    so both [B,H,S,D] and [B,S,H,D] layouts run with NO transpose or pad
 //    copies; the head dim D only needs D % 8 == 0 (8-element groups beyond
 //    D are masked in-kernel, DPAD = next multiple of 16).
 //
+// The kernels:
+//  * flash_fwd_bf16_kernel ("v2"): K row-major and V transposed in LDS
+//    (v2_stage), online softmax with per-tile rescale; the previous tile's
+//    PV completes before the rescale decision (textbook order). The whole
+//    per-tile compute is v2_tile_step.
+//  * flash_blend_bf16_kernel: a context loop around v2's tile loop — the
+//    same v2_stage and v2_tile_step, with its own QS and the context's key
+//    count as the key bound.
+//  * flash_fwd_bf16_v3: the same geometry with double-buffered row-major
+//    tiles, hardware-transpose V reads, async staging and defer-max; it
+//    shares the helpers, not the tile step.
+//
+// These kernels sit at the 256-VGPR edge, and how far a piece is shared is
+// set by what keeps their register allocation (table and method in
+// docs/kernels.md): a helper is optimised on its own before it is inlined,
+// so one that owns an unrolled r loop hands the kernel 16 hoisted broadcast
+// addresses or d-guards instead of a loop. That is why load_q_frags and
+// store_row take one q-subtile / one register and the kernels keep those
+// loops, why the per-row rescale loop is spelled out in v2_tile_step and
+// in v3, and why v3 keeps its own epilogue.
+//
 // UNet shapes: D 40(->48), 80, 160; SDXL 64; VAE (D=512) takes the composed
 // fallback path in ext.hip.
 #include "common.h"
+
+#include <type_traits>
+#include <utility>
 
 __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
   union {
@@ -36,19 +65,219 @@ struct AttnStrides {
   long ob, oh, or_;
 };
 
+// tile geometry of every kernel here, as functions of the padded head dim
+template <int DPAD>
+struct AttnGeom {
+  static constexpr int KVB = 64;  // two 32-key S^T sub-tiles per staging phase
+  static constexpr int PADK = 8;  // bf16 per-row pad: breaks ds_read_b128 conflicts
+  static constexpr int NC = DPAD / 16;              // QK^T k-chunks
+  static constexpr int DV = (DPAD + 31) / 32 * 32;  // PV d extent (32-col O tiles)
+  static constexpr int ND = DV / 32;                // PV d-chunks (O accum tiles)
+};
+
+// 32-row q-subtiles per wave (a block is 4 waves: 128 * QS q rows). The
+// kernels, the plan functions and the launchers' checks all read these.
+constexpr int v2_qs(int) { return 2; }
+constexpr int v3_qs(int dpad) { return dpad <= 96 ? 2 : 1; }
+constexpr int blend_qs(int dpad) { return dpad <= 32 ? 2 : 1; }
+constexpr int blend_min_blocks(int dpad) { return dpad <= 96 ? 2 : 1; }
+
+// C layout of the 32x32 MFMA: the row that accumulator register r holds in
+// half-wave `half` (the column is lane % 32)
+__device__ __forceinline__ int crow(int r, int half) {
+  return (r & 3) + 8 * (r >> 2) + 4 * half;
+}
+
+// Q fragments of one 32-row q-subtile, read once; qq is this lane's q row.
+// B-frag of mfma(K,Q): lane holds Q[q=lq][d = c*16 + 8*half + i]. Rows past
+// Sq re-read the last row (never stored); 8-groups beyond D are zero. FOLD
+// (v3) multiplies by `fold` and rounds back to bf16 in the same pass.
+template <bool FOLD, int NC>
+__device__ __forceinline__ void load_q_frags(bf16x8 (&qf)[NC],
+                                             const __hip_bfloat16 *Qb,
+                                             long qr, long qq, long Sq, int D,
+                                             int half, float fold = 1.0f) {
+  const long qrow = (qq < Sq) ? qq : (Sq - 1);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int d0 = c * 16 + 8 * half;
+    bf16x8 qv = (bf16x8){};
+    if (d0 + 8 <= D) {
+      qv = *(const bf16x8 *)(Qb + qrow * qr + d0);
+      if constexpr (FOLD) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) qv[i] = (__bf16)((float)qv[i] * fold);
+      }
+    }
+    qf[c] = qv;
+  }
+}
+
+// one S^T[32k, 32q] score sub-tile -> the two PV A-fragments (16 keys each)
+__device__ __forceinline__ void p_relayout(const f32x16 &s, bf16x8 &pa0,
+                                           bf16x8 &pa1) {
+  unsigned pk[8];
+#pragma unroll
+  for (int t = 0; t < 8; ++t) pk[t] = pack_bf16(s[2 * t], s[2 * t + 1]);
+  auto r0 = __builtin_amdgcn_permlane32_swap(pk[0], pk[2], false, false);
+  auto r1 = __builtin_amdgcn_permlane32_swap(pk[1], pk[3], false, false);
+  unsigned frag[4] = {r0[0], r1[0], r0[1], r1[1]};
+  pa0 = *(bf16x8 *)frag;
+  auto r2 = __builtin_amdgcn_permlane32_swap(pk[4], pk[6], false, false);
+  auto r3 = __builtin_amdgcn_permlane32_swap(pk[5], pk[7], false, false);
+  unsigned frag1[4] = {r2[0], r3[0], r2[1], r3[1]};
+  pa1 = *(bf16x8 *)frag1;
+}
+
+// epilogue (v2, blend) of register r of the q-subtile whose first row is
+// qbase: o (times the row's f when SCALED) rounded to bf16, column-per-lane
+// scatter (widen later, T21)
+template <bool SCALED, int ND>
+__device__ __forceinline__ void store_row(const f32x16 (&o)[ND], float f,
+                                          int r, __hip_bfloat16 *Ob, long orow,
+                                          long qbase, long Sq, int D, int lq,
+                                          int half) {
+  const int qrow = crow(r, half);
+  float a = 1.0f;
+  if constexpr (SCALED) a = __shfl(f, qrow, WAVE);
+  const long qq = qbase + qrow;
+  if (qq >= Sq) return;
+#pragma unroll
+  for (int d = 0; d < ND; ++d)
+    if (d * 32 + lq < D)
+      Ob[qq * orow + d * 32 + lq] = f2bf(SCALED ? o[d][r] * a : o[d][r]);
+}
+
+// ---------------------------------------------------------------------------
+// v2 pieces: LDS tiles (K row-major padded, V transposed for contiguous
+// B-fragment reads), the cooperative stage and the per-tile compute. The
+// callers own the kv loop and its two block-uniform barriers per tile.
+// ---------------------------------------------------------------------------
+template <int DPAD>
+using V2KTile = __bf16[AttnGeom<DPAD>::KVB][DPAD + AttnGeom<DPAD>::PADK];
+template <int DPAD>
+using V2VTile =
+    __bf16[AttnGeom<DPAD>::DV][AttnGeom<DPAD>::KVB + AttnGeom<DPAD>::PADK];
+
+// zero vt's pad rows once (D..DV); they are never re-staged
+template <int DPAD>
+__device__ __forceinline__ void v2_zero_vt_pad(V2VTile<DPAD> &vt, int D) {
+  using G = AttnGeom<DPAD>;
+  for (int idx = threadIdx.x + (D / 8) * 8 * (G::KVB + G::PADK);
+       idx < G::DV * (G::KVB + G::PADK); idx += 256)
+    ((__bf16 *)vt)[idx] = (__bf16)0.0f;
+}
+
+// cooperative K/V stage of keys [kv, kv + KVB): 256 threads, 8 bf16 each per
+// step; keys at or past len and 8-groups beyond D are staged as zero
+template <int DPAD>
+__device__ __forceinline__ void v2_stage(V2KTile<DPAD> &kt, V2VTile<DPAD> &vt,
+                                         const __hip_bfloat16 *Kb,
+                                         const __hip_bfloat16 *Vb, long kr,
+                                         long vr, long kv, long len, int D) {
+  for (int idx = threadIdx.x; idx < AttnGeom<DPAD>::KVB * (DPAD / 8);
+       idx += 256) {
+    const int r = idx / (DPAD / 8);     // key row in tile
+    const int c8 = idx % (DPAD / 8);    // 8-elem column group
+    bf16x8 kvec = (bf16x8){};
+    bf16x8 vvec = (bf16x8){};
+    if (kv + r < len && c8 * 8 + 8 <= D) {
+      kvec = *(const bf16x8 *)(Kb + (kv + r) * kr + c8 * 8);
+      vvec = *(const bf16x8 *)(Vb + (kv + r) * vr + c8 * 8);
+    }
+    *(bf16x8 *)&kt[r][c8 * 8] = kvec;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) vt[c8 * 8 + j][r] = vvec[j];
+  }
+}
+
+// the staged tile against every q-subtile of the wave: two S^T[32k, 32q]
+// k-sub-tiles, merged softmax, O rescale, PV. Keys at or past len are masked.
+template <int DPAD, int QS>
+__device__ __forceinline__ void v2_tile_step(
+    const V2KTile<DPAD> &kt, const V2VTile<DPAD> &vt,
+    const bf16x8 (&qf)[QS][AttnGeom<DPAD>::NC],
+    f32x16 (&o)[QS][AttnGeom<DPAD>::ND], float (&m)[QS], float (&l)[QS],
+    long kv, long len, float l2scale, int lq, int half) {
+  using G = AttnGeom<DPAD>;
+#pragma unroll
+  for (int qs = 0; qs < QS; ++qs) {
+    f32x16 stile[2] = {(f32x16){}, (f32x16){}};
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+      for (int c = 0; c < G::NC; ++c) {
+        bf16x8 kf = *(const bf16x8 *)&kt[sub * 32 + lq][c * 16 + 8 * half];
+        stile[sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            kf, qf[qs][c], stile[sub], 0, 0, 0);
+      }
+
+    // softmax in base-2, in the accumulator registers: the fp32 scores
+    // take scale*log2(e) once, after the MFMA (Q is not pre-scaled), so the
+    // hot exponentials are bare v_exp2 with no per-element multiply
+    float pmax = -1e30f;
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int kk = sub * 32 + crow(r, half);
+        const float sv = (kv + kk < len) ? stile[sub][r] * l2scale : -1e30f;
+        stile[sub][r] = sv;
+        pmax = fmaxf(pmax, sv);
+      }
+    pmax = fmaxf(pmax, __shfl_xor(pmax, 32, WAVE));
+    const float mnew = fmaxf(m[qs], pmax);
+    const float alpha = __builtin_amdgcn_exp2f(m[qs] - mnew);
+    float rowsum = 0.f;
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        stile[sub][r] = __builtin_amdgcn_exp2f(stile[sub][r] - mnew);
+        rowsum += stile[sub][r];
+      }
+    rowsum += __shfl_xor(rowsum, 32, WAVE);
+    l[qs] = l[qs] * alpha + rowsum;
+    m[qs] = mnew;
+
+    // (not a helper shared with v3's deferred rescale: wrapping even the
+    // broadcast moved v2<80> from 88 to 132 and v2<160> from 736 to 856
+    // B/lane of scratch)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float a = __shfl(alpha, crow(r, half), WAVE);
+#pragma unroll
+      for (int d = 0; d < G::ND; ++d) o[qs][d][r] *= a;
+    }
+
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {
+      bf16x8 pa0, pa1;
+      p_relayout(stile[sub], pa0, pa1);
+#pragma unroll
+      for (int d = 0; d < G::ND; ++d) {
+        bf16x8 v0 = *(const bf16x8 *)&vt[d * 32 + lq][sub * 32 + 8 * half];
+        o[qs][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa0, v0, o[qs][d],
+                                                           0, 0, 0);
+        bf16x8 v1 =
+            *(const bf16x8 *)&vt[d * 32 + lq][sub * 32 + 16 + 8 * half];
+        o[qs][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa1, v1, o[qs][d],
+                                                           0, 0, 0);
+      }
+    }
+  }
+}
+
 template <int DPAD>
 __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_kernel(
     const __hip_bfloat16 *__restrict__ Q, const __hip_bfloat16 *__restrict__ K,
     const __hip_bfloat16 *__restrict__ V, __hip_bfloat16 *__restrict__ O,
     int H, long Sq, long Sk, int D, float scale, AttnStrides st) {
-  constexpr int KVB = 64;  // two 32-key S^T sub-tiles per staging phase
-  constexpr int PADK = 8;   // bf16 per-row pad: breaks ds_read_b128 conflicts
-  constexpr int NC = DPAD / 16;              // QK^T k-chunks
-  constexpr int DV = (DPAD + 31) / 32 * 32;  // PV d extent (32-col O tiles)
-  constexpr int ND = DV / 32;                // PV d-chunks (O accum tiles)
+  using G = AttnGeom<DPAD>;
+  constexpr int QS = v2_qs(DPAD);
 
-  __shared__ __align__(16) __bf16 kt[KVB][DPAD + PADK];
-  __shared__ __align__(16) __bf16 vt[DV][KVB + PADK];
+  __shared__ __align__(16) V2KTile<DPAD> kt;
+  __shared__ __align__(16) V2VTile<DPAD> vt;
 
   // (an XCD-grouping remap — one head's q-blocks pinned to one XCD for
   // K/V L2 reuse — measured -13% on the S=4096 shape: the concentrated
@@ -60,161 +289,45 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_kernel(
   const int lane = threadIdx.x % WAVE;
   const int lq = lane % 32;   // q-row (softmax) / d-col (PV C) index
   const int half = lane / 32; // half-wave id
-  const long q0 = (long)qblk * 256 + wid * 64;
+  const long q0 = (long)qblk * (QS * 128) + wid * (QS * 32);
 
   const __hip_bfloat16 *Qb = Q + bb * st.qb + hh * st.qh;
   const __hip_bfloat16 *Kb = K + bb * st.kb + hh * st.kh;
   const __hip_bfloat16 *Vb = V + bb * st.vb + hh * st.vh;
   __hip_bfloat16 *Ob = O + bb * st.ob + hh * st.oh;
 
-  // Q fragments for the whole row-block, read once:
-  // B-frag of mfma(K,Q): lane holds Q[q=lq][d = c*16 + 8*half + i]
-  bf16x8 qf[2][NC];
+  bf16x8 qf[QS][G::NC];
 #pragma unroll
-  for (int qs = 0; qs < 2; ++qs) {
-    const long qq = q0 + qs * 32 + lq;
-    const long qrow = (qq < Sq) ? qq : (Sq - 1);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int d0 = c * 16 + 8 * half;
-      qf[qs][c] = (d0 + 8 <= D)
-                      ? *(const bf16x8 *)(Qb + qrow * st.qr + d0)
-                      : (bf16x8){};
-    }
-  }
+  for (int qs = 0; qs < QS; ++qs)
+    load_q_frags<false>(qf[qs], Qb, st.qr, q0 + qs * 32 + lq, Sq, D, half);
 
-  f32x16 o[2][ND];
+  f32x16 o[QS][G::ND];
 #pragma unroll
-  for (int qs = 0; qs < 2; ++qs)
+  for (int qs = 0; qs < QS; ++qs)
 #pragma unroll
-    for (int d = 0; d < ND; ++d) o[qs][d] = (f32x16){};
-  float m[2] = {-1e30f, -1e30f}, l[2] = {0.f, 0.f};
+    for (int d = 0; d < G::ND; ++d) o[qs][d] = (f32x16){};
+  float m[QS], l[QS];
+#pragma unroll
+  for (int qs = 0; qs < QS; ++qs) { m[qs] = -1e30f; l[qs] = 0.f; }
 
-  // zero vt's pad rows once (D..DV); they are never re-staged
-  for (int idx = threadIdx.x + (D / 8) * 8 * (KVB + PADK);
-       idx < DV * (KVB + PADK); idx += 256)
-    ((__bf16 *)vt)[idx] = (__bf16)0.0f;
+  v2_zero_vt_pad<DPAD>(vt, D);
+  const float l2scale = scale * 1.4426950408889634f;
 
-  for (long kv = 0; kv < Sk; kv += KVB) {
+  for (long kv = 0; kv < Sk; kv += G::KVB) {
     __syncthreads();  // previous tile's LDS reads complete
-    // cooperative K/V stage: 256 threads, 8 bf16 each per step
-    for (int idx = threadIdx.x; idx < KVB * (DPAD / 8); idx += 256) {
-      const int r = idx / (DPAD / 8);     // key row in tile
-      const int c8 = idx % (DPAD / 8);    // 8-elem column group
-      bf16x8 kvec = (bf16x8){};
-      bf16x8 vvec = (bf16x8){};
-      if (kv + r < Sk && c8 * 8 + 8 <= D) {
-        kvec = *(const bf16x8 *)(Kb + (kv + r) * st.kr + c8 * 8);
-        vvec = *(const bf16x8 *)(Vb + (kv + r) * st.vr + c8 * 8);
-      }
-      *(bf16x8 *)&kt[r][c8 * 8] = kvec;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) vt[c8 * 8 + j][r] = vvec[j];
-    }
+    v2_stage<DPAD>(kt, vt, Kb, Vb, st.kr, st.vr, kv, Sk, D);
     __syncthreads();
-
-    // per q-subtile: two S^T[32k, 32q] k-sub-tiles, merged softmax, PV
-#pragma unroll
-    for (int qs = 0; qs < 2; ++qs) {
-      f32x16 stile[2] = {(f32x16){}, (f32x16){}};
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          bf16x8 kf =
-              *(const bf16x8 *)&kt[sub * 32 + lq][c * 16 + 8 * half];
-          stile[sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              kf, qf[qs][c], stile[sub], 0, 0, 0);
-        }
-
-      // softmax in base-2: scores carry scale*log2(e) once, so the hot
-      // exponentials are bare v_exp2 with no per-element multiply
-      const float l2scale = scale * 1.4426950408889634f;
-      float p[2][16];
-      float pmax = -1e30f;
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kk = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-          float sv = (kv + kk < Sk) ? stile[sub][r] * l2scale : -1e30f;
-          p[sub][r] = sv;
-          pmax = fmaxf(pmax, sv);
-        }
-      pmax = fmaxf(pmax, __shfl_xor(pmax, 32, WAVE));
-      const float mnew = fmaxf(m[qs], pmax);
-      const float alpha = __builtin_amdgcn_exp2f(m[qs] - mnew);
-      float rowsum = 0.f;
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          p[sub][r] = __builtin_amdgcn_exp2f(p[sub][r] - mnew);
-          rowsum += p[sub][r];
-        }
-      rowsum += __shfl_xor(rowsum, 32, WAVE);
-      l[qs] = l[qs] * alpha + rowsum;
-      m[qs] = mnew;
-
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int qrow = (r & 3) + 8 * (r >> 2) + 4 * half;
-        const float a = __shfl(alpha, qrow, WAVE);
-#pragma unroll
-        for (int d = 0; d < ND; ++d) o[qs][d][r] *= a;
-      }
-
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub) {
-        unsigned pk[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-          pk[t] = pack_bf16(p[sub][2 * t], p[sub][2 * t + 1]);
-        bf16x8 pa0, pa1;
-        {
-          auto r0 =
-              __builtin_amdgcn_permlane32_swap(pk[0], pk[2], false, false);
-          auto r1 =
-              __builtin_amdgcn_permlane32_swap(pk[1], pk[3], false, false);
-          unsigned frag[4] = {r0[0], r1[0], r0[1], r1[1]};
-          pa0 = *(bf16x8 *)frag;
-          auto r2 =
-              __builtin_amdgcn_permlane32_swap(pk[4], pk[6], false, false);
-          auto r3 =
-              __builtin_amdgcn_permlane32_swap(pk[5], pk[7], false, false);
-          unsigned frag1[4] = {r2[0], r3[0], r2[1], r3[1]};
-          pa1 = *(bf16x8 *)frag1;
-        }
-#pragma unroll
-        for (int d = 0; d < ND; ++d) {
-          bf16x8 v0 =
-              *(const bf16x8 *)&vt[d * 32 + lq][sub * 32 + 8 * half];
-          o[qs][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              pa0, v0, o[qs][d], 0, 0, 0);
-          bf16x8 v1 =
-              *(const bf16x8 *)&vt[d * 32 + lq][sub * 32 + 16 + 8 * half];
-          o[qs][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              pa1, v1, o[qs][d], 0, 0, 0);
-        }
-      }
-    }
+    v2_tile_step<DPAD, QS>(kt, vt, qf, o, m, l, kv, Sk, l2scale, lq, half);
   }
 
-  // epilogue: O /= l, store (column-per-lane scatter; widen later, T21)
+  // epilogue: O /= l, store
 #pragma unroll
-  for (int qs = 0; qs < 2; ++qs) {
+  for (int qs = 0; qs < QS; ++qs) {
     const float linv = 1.0f / fmaxf(l[qs], 1e-30f);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int qrow = (r & 3) + 8 * (r >> 2) + 4 * half;
-      const float inv = __shfl(linv, qrow, WAVE);
-      const long qq = q0 + qs * 32 + qrow;
-      if (qq >= Sq) continue;
-#pragma unroll
-      for (int d = 0; d < ND; ++d)
-        if (d * 32 + lq < D)
-          Ob[qq * st.or_ + d * 32 + lq] = f2bf(o[qs][d][r] * inv);
-    }
+    for (int r = 0; r < 16; ++r)
+      store_row<true>(o[qs], linv, r, Ob, st.or_, q0 + qs * 32, Sq, D, lq,
+                      half);
   }
 }
 
@@ -233,16 +346,14 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_kernel(
 //    which fp32 accumulation absorbs (THR=8 -> P<=256).
 //  * s_setprio(1) brackets around the MFMA clusters (T5).
 // ---------------------------------------------------------------------------
-template <int DPAD, int QS = (DPAD <= 96 ? 2 : 1)>
+template <int DPAD, int QS = v3_qs(DPAD)>
 __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
     const __hip_bfloat16 *__restrict__ Q, const __hip_bfloat16 *__restrict__ K,
     const __hip_bfloat16 *__restrict__ V, __hip_bfloat16 *__restrict__ O,
     int H, long Sq, long Sk, int D, float scale, AttnStrides st) {
-  constexpr int KVB = 64;
-  constexpr int PADK = 8;
-  constexpr int NC = DPAD / 16;
-  constexpr int DV = (DPAD + 31) / 32 * 32;
-  constexpr int ND = DV / 32;
+  using G = AttnGeom<DPAD>;
+  constexpr int KVB = G::KVB, PADK = G::PADK, NC = G::NC, DV = G::DV,
+                ND = G::ND;
   // tr-read conflict pad: the residual ~6% SQ_LDS_BANK_CONFLICT is
   // tr-instruction-intrinsic (a +16 stride variant measured identical;
   // guide T10: addr swizzles don't move tr_read conflict classes)
@@ -307,22 +418,9 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
   const float l2scale = scale * 1.4426950408889634f;
   bf16x8 qf[QS][NC];
 #pragma unroll
-  for (int qs = 0; qs < QS; ++qs) {
-    const long qq = q0 + qs * 32 + lq;
-    const long qrow = (qq < Sq) ? qq : (Sq - 1);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int d0 = c * 16 + 8 * half;
-      bf16x8 qv = (bf16x8){};
-      if (d0 + 8 <= D) {
-        qv = *(const bf16x8 *)(Qb + qrow * st.qr + d0);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-          qv[i] = (__bf16)((float)qv[i] * l2scale);
-      }
-      qf[qs][c] = qv;
-    }
-  }
+  for (int qs = 0; qs < QS; ++qs)
+    load_q_frags<true>(qf[qs], Qb, st.qr, q0 + qs * 32 + lq, Sq, D, half,
+                       l2scale);
 
   // per-lane tr-read base LDS byte address (probe-decoded mapping): the
   // per-read row/col deltas are added as small unsigned offsets
@@ -377,19 +475,21 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
         *(bf16x8 *)((v ? &vt2[cur][0][0] : &kt[cur][0][0]) + eoff[s]) =
             *(const bf16x8 *)pp[s];
       }
-      if (kv + 2 * KVB <= Sk) {
+    }
+    // piece pointers -> the next tile: a uniform advance while it is full,
+    // the clamped re-derivation when it is the ragged last one
+    if (kv + 2 * KVB <= Sk) {
 #pragma unroll
-        for (int s = 0; s < NST; ++s)
-          pp[s] += (threadIdx.x + s * 256 >= NG) ? vdelta : kdelta;
-      } else if (kv + KVB < Sk) {
+      for (int s = 0; s < NST; ++s)
+        pp[s] += (threadIdx.x + s * 256 >= NG) ? vdelta : kdelta;
+    } else if (kv + KVB < Sk) {
 #pragma unroll
-        for (int s = 0; s < NST; ++s) {
-          int sr, sc; bool v; piece(s, sr, sc, v);
-          const long rr = kv + KVB + sr;
-          const long r = (rr < Sk) ? rr : (Sk - 1);
-          const int cg = (sc <= dmax) ? sc : dmax;
-          pp[s] = (v ? Vb + r * st.vr : Kb + r * st.kr) + cg * 8;
-        }
+      for (int s = 0; s < NST; ++s) {
+        int sr, sc; bool v; piece(s, sr, sc, v);
+        const long rr = kv + KVB + sr;
+        const long r = (rr < Sk) ? rr : (Sk - 1);
+        const int cg = (sc <= dmax) ? sc : dmax;
+        pp[s] = (v ? Vb + r * st.vr : Kb + r * st.kr) + cg * 8;
       }
     }
     __syncthreads();
@@ -397,20 +497,6 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
     // this tile's compute (the compiler places the vmcnt at first reuse)
     if constexpr (ASYNC) {
       if (kv + KVB < Sk) {
-        if (kv + 2 * KVB <= Sk) {
-#pragma unroll
-          for (int s = 0; s < NST; ++s)
-            pp[s] += (threadIdx.x + s * 256 >= NG) ? vdelta : kdelta;
-        } else {
-#pragma unroll
-          for (int s = 0; s < NST; ++s) {
-            int sr, sc; bool v; piece(s, sr, sc, v);
-            const long rr = kv + KVB + sr;
-            const long r = (rr < Sk) ? rr : (Sk - 1);
-            const int cg = (sc <= dmax) ? sc : dmax;
-            pp[s] = (v ? Vb + r * st.vr : Kb + r * st.kr) + cg * 8;
-          }
-        }
 #pragma unroll
         for (int s = 0; s < NST; ++s) stg[s] = *(const bf16x8 *)pp[s];
       }
@@ -445,7 +531,7 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
         for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int kk = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            const int kk = sub * 32 + crow(r, half);
             if (kv + kk >= Sk) stile[sub][r] = -1e30f;
             pmax = fmaxf(pmax, stile[sub][r]);
           }
@@ -460,8 +546,7 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
         m[qs] = mnew;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int qrow = (r & 3) + 8 * (r >> 2) + 4 * half;
-          const float a = __shfl(alpha, qrow, WAVE);
+          const float a = __shfl(alpha, crow(r, half), WAVE);
 #pragma unroll
           for (int d = 0; d < ND; ++d) o[qs][d][r] *= a;
         }
@@ -479,25 +564,8 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
 
 #pragma unroll
       for (int sub = 0; sub < 2; ++sub) {
-        unsigned pk[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-          pk[t] = pack_bf16(stile[sub][2 * t], stile[sub][2 * t + 1]);
         bf16x8 pa[2];
-        {
-          auto r0 =
-              __builtin_amdgcn_permlane32_swap(pk[0], pk[2], false, false);
-          auto r1 =
-              __builtin_amdgcn_permlane32_swap(pk[1], pk[3], false, false);
-          unsigned frag[4] = {r0[0], r1[0], r0[1], r1[1]};
-          pa[0] = *(bf16x8 *)frag;
-          auto r2 =
-              __builtin_amdgcn_permlane32_swap(pk[4], pk[6], false, false);
-          auto r3 =
-              __builtin_amdgcn_permlane32_swap(pk[5], pk[7], false, false);
-          unsigned frag1[4] = {r2[0], r3[0], r2[1], r3[1]};
-          pa[1] = *(bf16x8 *)frag1;
-        }
+        p_relayout(stile[sub], pa[0], pa[1]);
         // PV with tr-read V fragments: per 16-key chunk, 2 transpose
         // reads per d-tile deliver V[k..k+7][dcol] straight from the
         // row-major tile (guide T10; mapping from tools/tr16_probe.py)
@@ -549,14 +617,15 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
     }
   }
 
+  // epilogue: store_row's sequence, spelled out. Through the helper the
+  // d-guards leave the r loop and DPAD 80 and 96 spill 20 and 4 B/lane more
 #pragma unroll
   for (int qs = 0; qs < QS; ++qs) {
     const float linv = 1.0f / fmaxf(l[qs], 1e-30f);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int qrow = (r & 3) + 8 * (r >> 2) + 4 * half;
-      const float inv = __shfl(linv, qrow, WAVE);
-      const long qq = q0 + qs * 32 + qrow;
+      const float inv = __shfl(linv, crow(r, half), WAVE);
+      const long qq = q0 + qs * 32 + crow(r, half);
       if (qq >= Sq) continue;
 #pragma unroll
       for (int d = 0; d < ND; ++d)
@@ -569,9 +638,8 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
 // ---------------------------------------------------------------------------
 // multi-context blend: out[b,s,h,:] = sum_c W[b,c,s] * attn(q[b,s,h], K_c, V_c)
 // with K_c/V_c = batch row kv_index[b*C + c] of K/V, kv_len[row] keys long.
-// The v2 kernel (4 waves, 64-key LDS tiles, swapped QK^T, in-register
-// softmax, permlane P relayout, fp32 score scaling after the MFMA) with a
-// context loop around the tile loop: Q fragments are read once; every
+// The v2 pieces (v2_stage, v2_tile_step: fp32 score scaling after the MFMA)
+// with a context loop around the tile loop: Q fragments are read once; every
 // context restarts m/l/o, walks its own tiles, and folds o * (w / l) into
 // a second fp32 accumulator; the output is rounded to bf16 once, after the
 // last context. The row and its length depend on (b, c) only, so every
@@ -585,9 +653,6 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
 // scratch (checked with -Rpass-analysis=kernel-resource-usage; table in
 // docs/kernels.md).
 // ---------------------------------------------------------------------------
-constexpr int blend_qs(int dpad) { return dpad <= 32 ? 2 : 1; }
-constexpr int blend_min_blocks(int dpad) { return dpad <= 96 ? 2 : 1; }
-
 template <int DPAD, int QS = blend_qs(DPAD)>
 __launch_bounds__(256, blend_min_blocks(DPAD)) __global__
 void flash_blend_bf16_kernel(
@@ -596,14 +661,10 @@ void flash_blend_bf16_kernel(
     int H, long Sq, long Sk, int D, float scale, AttnStrides st, int C,
     int Bk, const int *__restrict__ kv_index, const int *__restrict__ kv_len,
     const float *__restrict__ W, long wb, long wc) {
-  constexpr int KVB = 64;
-  constexpr int PADK = 8;
-  constexpr int NC = DPAD / 16;
-  constexpr int DV = (DPAD + 31) / 32 * 32;
-  constexpr int ND = DV / 32;
+  using G = AttnGeom<DPAD>;
 
-  __shared__ __align__(16) __bf16 kt[KVB][DPAD + PADK];
-  __shared__ __align__(16) __bf16 vt[DV][KVB + PADK];
+  __shared__ __align__(16) V2KTile<DPAD> kt;
+  __shared__ __align__(16) V2VTile<DPAD> vt;
 
   const int bh = blockIdx.y;
   const int qblk = blockIdx.x;
@@ -617,31 +678,18 @@ void flash_blend_bf16_kernel(
   const __hip_bfloat16 *Qb = Q + bb * st.qb + hh * st.qh;
   __hip_bfloat16 *Ob = O + bb * st.ob + hh * st.oh;
 
-  bf16x8 qf[QS][NC];
+  bf16x8 qf[QS][G::NC];
 #pragma unroll
-  for (int qs = 0; qs < QS; ++qs) {
-    const long qq = q0 + qs * 32 + lq;
-    const long qrow = (qq < Sq) ? qq : (Sq - 1);
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int d0 = c * 16 + 8 * half;
-      qf[qs][c] = (d0 + 8 <= D)
-                      ? *(const bf16x8 *)(Qb + qrow * st.qr + d0)
-                      : (bf16x8){};
-    }
-  }
+  for (int qs = 0; qs < QS; ++qs)
+    load_q_frags<false>(qf[qs], Qb, st.qr, q0 + qs * 32 + lq, Sq, D, half);
 
-  f32x16 acc[QS][ND];
+  f32x16 acc[QS][G::ND];
 #pragma unroll
   for (int qs = 0; qs < QS; ++qs)
 #pragma unroll
-    for (int d = 0; d < ND; ++d) acc[qs][d] = (f32x16){};
+    for (int d = 0; d < G::ND; ++d) acc[qs][d] = (f32x16){};
 
-  // zero vt's pad rows once (D..DV); they are never re-staged
-  for (int idx = threadIdx.x + (D / 8) * 8 * (KVB + PADK);
-       idx < DV * (KVB + PADK); idx += 256)
-    ((__bf16 *)vt)[idx] = (__bf16)0.0f;
-
+  v2_zero_vt_pad<DPAD>(vt, D);
   const float l2scale = scale * 1.4426950408889634f;
 
   for (int cx = 0; cx < C; ++cx) {
@@ -655,120 +703,25 @@ void flash_blend_bf16_kernel(
     const __hip_bfloat16 *Kb = K + row * st.kb + hh * st.kh;
     const __hip_bfloat16 *Vb = V + row * st.vb + hh * st.vh;
 
-    f32x16 o[QS][ND];
+    f32x16 o[QS][G::ND];
 #pragma unroll
     for (int qs = 0; qs < QS; ++qs)
 #pragma unroll
-      for (int d = 0; d < ND; ++d) o[qs][d] = (f32x16){};
+      for (int d = 0; d < G::ND; ++d) o[qs][d] = (f32x16){};
     float m[QS], l[QS];
 #pragma unroll
     for (int qs = 0; qs < QS; ++qs) { m[qs] = -1e30f; l[qs] = 0.f; }
 
-    for (long kv = 0; kv < len; kv += KVB) {
+    for (long kv = 0; kv < len; kv += G::KVB) {
       __syncthreads();  // previous tile's (or context's) LDS reads complete
-      for (int idx = threadIdx.x; idx < KVB * (DPAD / 8); idx += 256) {
-        const int r = idx / (DPAD / 8);
-        const int c8 = idx % (DPAD / 8);
-        bf16x8 kvec = (bf16x8){};
-        bf16x8 vvec = (bf16x8){};
-        if (kv + r < len && c8 * 8 + 8 <= D) {
-          kvec = *(const bf16x8 *)(Kb + (kv + r) * st.kr + c8 * 8);
-          vvec = *(const bf16x8 *)(Vb + (kv + r) * st.vr + c8 * 8);
-        }
-        *(bf16x8 *)&kt[r][c8 * 8] = kvec;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) vt[c8 * 8 + j][r] = vvec[j];
-      }
+      v2_stage<DPAD>(kt, vt, Kb, Vb, st.kr, st.vr, kv, len, D);
       __syncthreads();
-
-#pragma unroll
-      for (int qs = 0; qs < QS; ++qs) {
-        f32x16 stile[2] = {(f32x16){}, (f32x16){}};
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-          for (int c = 0; c < NC; ++c) {
-            bf16x8 kf =
-                *(const bf16x8 *)&kt[sub * 32 + lq][c * 16 + 8 * half];
-            stile[sub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                kf, qf[qs][c], stile[sub], 0, 0, 0);
-          }
-
-        // base-2 softmax in the accumulator registers; the fp32 scores
-        // are scaled here, after the MFMA (Q is not pre-scaled)
-        float pmax = -1e30f;
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int kk = sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            const float sv =
-                (kv + kk < len) ? stile[sub][r] * l2scale : -1e30f;
-            stile[sub][r] = sv;
-            pmax = fmaxf(pmax, sv);
-          }
-        pmax = fmaxf(pmax, __shfl_xor(pmax, 32, WAVE));
-        const float mnew = fmaxf(m[qs], pmax);
-        const float alpha = __builtin_amdgcn_exp2f(m[qs] - mnew);
-        float rowsum = 0.f;
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            stile[sub][r] = __builtin_amdgcn_exp2f(stile[sub][r] - mnew);
-            rowsum += stile[sub][r];
-          }
-        rowsum += __shfl_xor(rowsum, 32, WAVE);
-        l[qs] = l[qs] * alpha + rowsum;
-        m[qs] = mnew;
-
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int qrow = (r & 3) + 8 * (r >> 2) + 4 * half;
-          const float a = __shfl(alpha, qrow, WAVE);
-#pragma unroll
-          for (int d = 0; d < ND; ++d) o[qs][d][r] *= a;
-        }
-
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-          unsigned pk[8];
-#pragma unroll
-          for (int t = 0; t < 8; ++t)
-            pk[t] = pack_bf16(stile[sub][2 * t], stile[sub][2 * t + 1]);
-          bf16x8 pa0, pa1;
-          {
-            auto r0 =
-                __builtin_amdgcn_permlane32_swap(pk[0], pk[2], false, false);
-            auto r1 =
-                __builtin_amdgcn_permlane32_swap(pk[1], pk[3], false, false);
-            unsigned frag[4] = {r0[0], r1[0], r0[1], r1[1]};
-            pa0 = *(bf16x8 *)frag;
-            auto r2 =
-                __builtin_amdgcn_permlane32_swap(pk[4], pk[6], false, false);
-            auto r3 =
-                __builtin_amdgcn_permlane32_swap(pk[5], pk[7], false, false);
-            unsigned frag1[4] = {r2[0], r3[0], r2[1], r3[1]};
-            pa1 = *(bf16x8 *)frag1;
-          }
-#pragma unroll
-          for (int d = 0; d < ND; ++d) {
-            bf16x8 v0 =
-                *(const bf16x8 *)&vt[d * 32 + lq][sub * 32 + 8 * half];
-            o[qs][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                pa0, v0, o[qs][d], 0, 0, 0);
-            bf16x8 v1 =
-                *(const bf16x8 *)&vt[d * 32 + lq][sub * 32 + 16 + 8 * half];
-            o[qs][d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                pa1, v1, o[qs][d], 0, 0, 0);
-          }
-        }
-      }
+      v2_tile_step<DPAD, QS>(kt, vt, qf, o, m, l, kv, len, l2scale, lq, half);
     }
 
     // fold this context in: acc += o * (w / l). Lane lq holds its own
     // row's l and loads its own row's weight; the per-row lane broadcast
-    // is the one the 1/l epilogue uses
+    // is row_factor's
 #pragma unroll
     for (int qs = 0; qs < QS; ++qs) {
       const long qq = q0 + qs * 32 + lq;
@@ -776,28 +729,20 @@ void flash_blend_bf16_kernel(
       const float wl = wv / fmaxf(l[qs], 1e-30f);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int qrow = (r & 3) + 8 * (r >> 2) + 4 * half;
-        const float f = __shfl(wl, qrow, WAVE);
+        const float f = __shfl(wl, crow(r, half), WAVE);
 #pragma unroll
-        for (int d = 0; d < ND; ++d) acc[qs][d][r] += o[qs][d][r] * f;
+        for (int d = 0; d < G::ND; ++d) acc[qs][d][r] += o[qs][d][r] * f;
       }
     }
   }
 
   // one bf16 rounding of the blended row
 #pragma unroll
-  for (int qs = 0; qs < QS; ++qs) {
+  for (int qs = 0; qs < QS; ++qs)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int qrow = (r & 3) + 8 * (r >> 2) + 4 * half;
-      const long qq = q0 + qs * 32 + qrow;
-      if (qq >= Sq) continue;
-#pragma unroll
-      for (int d = 0; d < ND; ++d)
-        if (d * 32 + lq < D)
-          Ob[qq * st.or_ + d * 32 + lq] = f2bf(acc[qs][d][r]);
-    }
-  }
+    for (int r = 0; r < 16; ++r)
+      store_row<false>(acc[qs], 1.0f, r, Ob, st.or_, q0 + qs * 32, Sq, D, lq,
+                       half);
 }
 
 // ---------------------------------------------------------------------------
@@ -809,6 +754,36 @@ bool flash_supported(long d_head) {
 
 #ifdef __HIP_PLATFORM_AMD__
 static inline long round16(long d) { return (d + 15) / 16 * 16; }
+
+// Calls f(std::integral_constant<int, DP>) for the instantiated padded head
+// dim DP equal to dpad; any other dpad is an error.
+template <class F, int... DP>
+static void dispatch_dpad_in(long dpad, const char *who, F &&f,
+                             std::integer_sequence<int, DP...>) {
+  const bool found =
+      ((dpad == DP ? (f(std::integral_constant<int, DP>{}), true) : false) ||
+       ...);
+  TORCH_CHECK(found, who, ": unsupported padded head dim ", dpad);
+}
+template <class F>
+static void dispatch_dpad(long dpad, const char *who, F &&f) {
+  dispatch_dpad_in(dpad, who, f,
+                   std::integer_sequence<int, 32, 48, 64, 80, 96, 112, 128,
+                                         144, 160, 176, 192>{});
+}
+
+// q/k/v/out: "bhsd" ([B,H,S,D]) or "bshd" ([B,S,H,D]) views
+static AttnStrides attn_strides(const torch::Tensor &q, const torch::Tensor &k,
+                                const torch::Tensor &v,
+                                const torch::Tensor &out, bool bshd) {
+  const int h = bshd ? 2 : 1, r = bshd ? 1 : 2;
+  AttnStrides st;
+  st.qb = q.stride(0); st.qh = q.stride(h); st.qr = q.stride(r);
+  st.kb = k.stride(0); st.kh = k.stride(h); st.kr = k.stride(r);
+  st.vb = v.stride(0); st.vh = v.stride(h); st.vr = v.stride(r);
+  st.ob = out.stride(0); st.oh = out.stride(h); st.or_ = out.stride(r);
+  return st;
+}
 
 // Which kernel serves an attention call: {"v2" | "v3" | "composed", padded
 // head dim, q rows per workgroup}. "composed" is the GEMM + row_softmax_
@@ -832,8 +807,8 @@ std::tuple<std::string, long, long> attention_plan(long d_head, long sk,
   // prologue/epilogue spills are off the hot loop: +24% at D=80, +7% at
   // D=160); the short-Sk cross shapes (Sk=77) stay on v2
   const bool v2 = force == 2 || (force == 0 && dpad > 64 && sk < 256);
-  if (v2) return {"v2", dpad, 256};
-  return {"v3", dpad, dpad <= 96 ? 256 : 128};  // QS * 128
+  if (v2) return {"v2", dpad, 128 * v2_qs((int)dpad)};
+  return {"v3", dpad, 128 * v3_qs((int)dpad)};
 }
 
 // qkv layout: "bhsd" (q.size = [B,H,S,D]) or "bshd" ([B,S,H,D]); tensors
@@ -850,64 +825,29 @@ static torch::Tensor flash_attention_raw(torch::Tensor q, torch::Tensor k,
               "flash: D must be unit-stride");
   auto out = bshd ? torch::empty({B, Sq, H, D}, q.options())
                   : torch::empty({B, H, Sq, D}, q.options());
-  AttnStrides st;
-  if (bshd) {
-    st.qb = q.stride(0); st.qh = q.stride(2); st.qr = q.stride(1);
-    st.kb = k.stride(0); st.kh = k.stride(2); st.kr = k.stride(1);
-    st.vb = v.stride(0); st.vh = v.stride(2); st.vr = v.stride(1);
-    st.ob = out.stride(0); st.oh = out.stride(2); st.or_ = out.stride(1);
-  } else {
-    st.qb = q.stride(0); st.qh = q.stride(1); st.qr = q.stride(2);
-    st.kb = k.stride(0); st.kh = k.stride(1); st.kr = k.stride(2);
-    st.vb = v.stride(0); st.vh = v.stride(1); st.vr = v.stride(2);
-    st.ob = out.stride(0); st.oh = out.stride(1); st.or_ = out.stride(2);
-  }
-  const long DP = round16(D);
-  dim3 block(256);
+  const AttnStrides st = attn_strides(q, k, v, out, bshd);
+  const dim3 block(256);
   auto stream = cur_stream();
   // the plan decides v2 vs v3 and the block's q-row extent; nothing else
-  const auto [kernel, dpad_, qrows] = attention_plan(D, Sk, force);
-  TORCH_CHECK(dpad_ == DP, "flash: plan/launch padded head dim mismatch");
+  const auto [kernel, dpad, qrows] = attention_plan(D, Sk, force);
+  TORCH_CHECK(dpad == round16(D),
+              "flash: plan/launch padded head dim mismatch");
   const bool run_v2 = kernel == "v2";
+  const long rows = qrows;  // (a structured binding cannot be captured)
+  const dim3 grid((unsigned)((Sq + rows - 1) / rows), (unsigned)(B * H));
 
-  const dim3 grid((unsigned)((Sq + qrows - 1) / qrows), (unsigned)(B * H));
-
-#define LAUNCH_FLASH(DP_)                                                   \
-  do {                                                                      \
-    if (run_v2) {                                                           \
-      hipLaunchKernelGGL(flash_fwd_bf16_kernel<DP_>, grid, block, 0,        \
-                         stream, (const __hip_bfloat16 *)q.data_ptr(),      \
-                         (const __hip_bfloat16 *)k.data_ptr(),              \
-                         (const __hip_bfloat16 *)v.data_ptr(),              \
-                         (__hip_bfloat16 *)out.data_ptr(), (int)H, Sq, Sk,  \
-                         (int)D, (float)scale, st);                         \
-    } else {                                                                \
-      TORCH_CHECK(qrows == (DP_ <= 96 ? 256 : 128),                         \
-                  "flash: plan rows do not match the v3 instantiation");    \
-      hipLaunchKernelGGL(flash_fwd_bf16_v3<DP_>, grid, block, 0, stream,    \
-                         (const __hip_bfloat16 *)q.data_ptr(),              \
-                         (const __hip_bfloat16 *)k.data_ptr(),              \
-                         (const __hip_bfloat16 *)v.data_ptr(),              \
-                         (__hip_bfloat16 *)out.data_ptr(), (int)H, Sq, Sk,  \
-                         (int)D, (float)scale, st);                         \
-    }                                                                       \
-  } while (0)
-
-  switch (DP) {
-    case 32: LAUNCH_FLASH(32); break;
-    case 48: LAUNCH_FLASH(48); break;
-    case 64: LAUNCH_FLASH(64); break;
-    case 80: LAUNCH_FLASH(80); break;
-    case 96: LAUNCH_FLASH(96); break;
-    case 112: LAUNCH_FLASH(112); break;
-    case 128: LAUNCH_FLASH(128); break;
-    case 144: LAUNCH_FLASH(144); break;
-    case 160: LAUNCH_FLASH(160); break;
-    case 176: LAUNCH_FLASH(176); break;
-    case 192: LAUNCH_FLASH(192); break;
-    default: TORCH_CHECK(false, "flash: unsupported padded head dim ", DP);
-  }
-#undef LAUNCH_FLASH
+  dispatch_dpad(dpad, "flash", [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    TORCH_CHECK(rows == 128 * (run_v2 ? v2_qs(DP) : v3_qs(DP)),
+                "flash: plan rows do not match the instantiation");
+    hipLaunchKernelGGL(
+        run_v2 ? flash_fwd_bf16_kernel<DP> : flash_fwd_bf16_v3<DP>, grid,
+        block, 0, stream, (const __hip_bfloat16 *)q.data_ptr(),
+        (const __hip_bfloat16 *)k.data_ptr(),
+        (const __hip_bfloat16 *)v.data_ptr(),
+        (__hip_bfloat16 *)out.data_ptr(), (int)H, Sq, Sk, (int)D,
+        (float)scale, st);
+  });
   return out;
 }
 
@@ -934,49 +874,29 @@ static torch::Tensor flash_blend_raw(torch::Tensor q, torch::Tensor k,
   const long Bk = k.size(0), Sk = k.size(1);
   const long C = w.size(1);
   auto out = torch::empty({B, Sq, H, D}, q.options());
-  AttnStrides st;
-  st.qb = q.stride(0); st.qh = q.stride(2); st.qr = q.stride(1);
-  st.kb = k.stride(0); st.kh = k.stride(2); st.kr = k.stride(1);
-  st.vb = v.stride(0); st.vh = v.stride(2); st.vr = v.stride(1);
-  st.ob = out.stride(0); st.oh = out.stride(2); st.or_ = out.stride(1);
+  const AttnStrides st = attn_strides(q, k, v, out, /*bshd=*/true);
   const long wb = w.size(0) == 1 ? 0 : w.stride(0), wc = w.stride(1);
-  const auto [DP, qrows] = attention_blend_plan(D);
-  const dim3 grid((unsigned)((Sq + qrows - 1) / qrows), (unsigned)(B * H));
+  const auto [dpad, qrows] = attention_blend_plan(D);
+  const long rows = qrows;  // (a structured binding cannot be captured)
+  const dim3 grid((unsigned)((Sq + rows - 1) / rows), (unsigned)(B * H));
   const dim3 block(256);
   auto stream = cur_stream();
   const int *len_ptr =
       kv_len.has_value() ? kv_len->data_ptr<int>() : (const int *)nullptr;
 
-#define LAUNCH_BLEND(DP_)                                                   \
-  do {                                                                      \
-    TORCH_CHECK(qrows == 128 * blend_qs(DP_),                               \
-                "flash_blend: plan rows do not match the instantiation");   \
-    hipLaunchKernelGGL(flash_blend_bf16_kernel<DP_>, grid, block, 0,        \
-                       stream, (const __hip_bfloat16 *)q.data_ptr(),        \
-                       (const __hip_bfloat16 *)k.data_ptr(),                \
-                       (const __hip_bfloat16 *)v.data_ptr(),                \
-                       (__hip_bfloat16 *)out.data_ptr(), (int)H, Sq, Sk,    \
-                       (int)D, (float)scale, st, (int)C, (int)Bk,           \
-                       kv_index.data_ptr<int>(), len_ptr,                   \
-                       w.data_ptr<float>(), wb, wc);                        \
-  } while (0)
-
-  switch (DP) {
-    case 32: LAUNCH_BLEND(32); break;
-    case 48: LAUNCH_BLEND(48); break;
-    case 64: LAUNCH_BLEND(64); break;
-    case 80: LAUNCH_BLEND(80); break;
-    case 96: LAUNCH_BLEND(96); break;
-    case 112: LAUNCH_BLEND(112); break;
-    case 128: LAUNCH_BLEND(128); break;
-    case 144: LAUNCH_BLEND(144); break;
-    case 160: LAUNCH_BLEND(160); break;
-    case 176: LAUNCH_BLEND(176); break;
-    case 192: LAUNCH_BLEND(192); break;
-    default:
-      TORCH_CHECK(false, "flash_blend: unsupported padded head dim ", DP);
-  }
-#undef LAUNCH_BLEND
+  dispatch_dpad(dpad, "flash_blend", [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    TORCH_CHECK(rows == 128 * blend_qs(DP),
+                "flash_blend: plan rows do not match the instantiation");
+    hipLaunchKernelGGL(flash_blend_bf16_kernel<DP>, grid, block, 0, stream,
+                       (const __hip_bfloat16 *)q.data_ptr(),
+                       (const __hip_bfloat16 *)k.data_ptr(),
+                       (const __hip_bfloat16 *)v.data_ptr(),
+                       (__hip_bfloat16 *)out.data_ptr(), (int)H, Sq, Sk,
+                       (int)D, (float)scale, st, (int)C, (int)Bk,
+                       kv_index.data_ptr<int>(), len_ptr,
+                       w.data_ptr<float>(), wb, wc);
+  });
   return out;
 }
 

@@ -281,6 +281,25 @@ class TestSingleContext:
         report(d, "C=1 w=1", worst)
         assert worst <= 1.0
 
+    @pytest.mark.parametrize("sk", [77, 150])
+    @pytest.mark.parametrize("d", [40, 80, 160])
+    def test_c1_unit_weight_is_v2_bit_for_bit(self, dev, d, sk):
+        """The blend and v2 run the same tile step, so one context of unit
+        weight is v2's sequence: w / l with w = 1 is 1 / l, 0 + o * f rounds
+        as o * f, and the per-row math does not depend on QS. Sq=70 crosses
+        a 32-row subtile inside a ragged block; Sk=77 is one ragged tile
+        after a full one, Sk=150 a multi-tile ragged walk."""
+        sq = 70
+        g = torch.Generator().manual_seed(1000 * d + sk)
+        q = torch.randn(B, sq, H, d, generator=g).bfloat16().to(dev)
+        k = torch.randn(B, sk, H, d, generator=g).bfloat16().to(dev)
+        v = torch.randn(B, sk, H, d, generator=g).bfloat16().to(dev)
+        w = torch.ones(1, 1, sq, device=dev)
+        blend = ops.attention_blend_bshd(q, k, v, w, [[0], [1]], None)
+        plain = ops.attention_bshd(q, k, v, variant="v2")
+        assert torch.isfinite(plain.float()).all()
+        assert torch.equal(blend, plain)
+
 
 class TestErrors:
     def _args(self, dev, d, dtype):

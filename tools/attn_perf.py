@@ -49,6 +49,8 @@ def main():
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--only", default=None, help="substring filter on tag")
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--variant", default=None, choices=["auto", "v2", "v3"],
+                    help="flash kernel to time (default: follow SDWD_ATTN)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "GPU required"
     results = {}
@@ -72,13 +74,13 @@ def main():
                     (qs.float() @ ks.float().transpose(-1, -2)) * scale,
                     dim=-1,
                 ) @ vs.float()
-                got = ops.attention(qs, ks, vs, scale).float()
+                got = ops.attention(qs, ks, vs, scale, args.variant).float()
                 err = (got - ref).abs().max().item()
                 rel = err / ref.abs().max().item()
             print(f"{tag}: max abs err {err:.4e} (rel {rel:.3e})")
             assert rel < 2e-2, f"{tag} numerics off"
             del ref, got, qs, ks, vs
-        ms = bench(lambda: ops.attention(q, k, v, scale),
+        ms = bench(lambda: ops.attention(q, k, v, scale, args.variant),
                    it=args.iters) * 1e3
         tf = flops(B, H, Sq, Sk, D) / (ms * 1e-3) / 1e12
         results[tag] = {"ms": round(ms, 3), "tf": round(tf, 1)}
