@@ -108,6 +108,25 @@ class OptionsRequest(BaseModel):
     model_config = {"extra": "allow"}
 
 
+_TOME_OPTIONS = (
+    "token_merging_ratio",
+    "token_merging_ratio_img2img",
+    "token_merging_ratio_hr",
+)
+
+
+def _tome_ratio(value) -> float:
+    """A token merging ratio option, clamped to [0, 0.9] like the host's
+    slider; anything that is not a number is a 422."""
+    try:
+        ratio = float(value or 0.0)
+    except (TypeError, ValueError):
+        raise HTTPException(422, f"token merging ratio: bad value {value!r}")
+    if ratio != ratio:
+        raise HTTPException(422, "token merging ratio: NaN")
+    return min(0.9, max(0.0, ratio))
+
+
 class ServerState:
     def __init__(self, engine: LocalEngine):
         self.engine = engine
@@ -120,6 +139,8 @@ class ServerState:
         self.default_clip_skip = 1
         self.ensd = 0
         self.randn_source = "CPU"  # "CPU" | "NV" (pipeline/noise.py)
+        # sdwui token_merging_ratio / _img2img / _hr options (0 = off)
+        self.token_merging = {k: 0.0 for k in _TOME_OPTIONS}
 
 
 def _b64_png(img: torch.Tensor) -> str:
@@ -619,6 +640,17 @@ def create_app(engine: Optional[LocalEngine] = None,
         except ValueError as exc:
             raise HTTPException(422, str(exc))
 
+    def _tome_ratios(req) -> Dict[str, float]:
+        """The three token merging ratios of a request: override_settings
+        beats the global option. Which one a pass uses is the pipeline's
+        business (token_merging_ratio_for)."""
+        ov = req.override_settings or {}
+        out = {}
+        for key in _TOME_OPTIONS:
+            value = ov[key] if key in ov else state.token_merging[key]
+            out[key] = _tome_ratio(value)
+        return out
+
     def _overrides(req: Txt2ImgRequest):
         """Per-request override_settings (sdwui convention)."""
         ov = req.override_settings or {}
@@ -680,6 +712,7 @@ def create_app(engine: Optional[LocalEngine] = None,
             seed_resize_from_h=req.seed_resize_from_h,
             eta_noise_seed_delta=ensd,
             randn_source=randn_source,
+            **_tome_ratios(req),
             tiling=req.tiling,
             s_churn=req.s_churn,
             s_tmin=req.s_tmin,
@@ -754,6 +787,7 @@ def create_app(engine: Optional[LocalEngine] = None,
             seed_resize_from_h=req.seed_resize_from_h,
             eta_noise_seed_delta=ensd,
             randn_source=randn_source,
+            **_tome_ratios(req),
             tiling=req.tiling,
             s_churn=req.s_churn,
             s_tmin=req.s_tmin,
@@ -793,6 +827,9 @@ def create_app(engine: Optional[LocalEngine] = None,
             state.randn_source = _randn_source(
                 extras["randn_source"] or "CPU"
             )
+        for key in _TOME_OPTIONS:
+            if key in extras:
+                state.token_merging[key] = _tome_ratio(extras[key])
         if req.sd_model_checkpoint and req.sd_model_checkpoint != state.current_model:
             name = req.sd_model_checkpoint
             if name not in available_models():
@@ -823,6 +860,7 @@ def create_app(engine: Optional[LocalEngine] = None,
             "CLIP_stop_at_last_layers": state.default_clip_skip,
             "eta_noise_seed_delta": state.ensd,
             "randn_source": state.randn_source,
+            **state.token_merging,
         }
 
     @app.get("/sdapi/v1/sd-models")

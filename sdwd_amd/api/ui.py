@@ -32,6 +32,9 @@ PAGE = """<!DOCTYPE html>
  steps <input id="steps" size="3" value="20"/>
  size <input id="size" size="4" value="512"/>
  seed <input id="seed" size="8" value="-1"/>
+ token merging <input id="tome" type="range" min="0" max="0.9" step="0.1"
+   value="0" oninput="document.getElementById('tome_v').textContent=this.value"/>
+ <span id="tome_v">0</span>
  <button>generate</button>
  <button type="button" onclick="fetch('/sdapi/v1/interrupt',{method:'POST'})">
    interrupt</button>
@@ -154,6 +157,8 @@ async function gen(ev){
     height: parseInt(document.getElementById('size').value),
     seed: parseInt(document.getElementById('seed').value),
   };
+  const tome = parseFloat(document.getElementById('tome').value);
+  if(tome > 0) body.override_settings = {token_merging_ratio: tome};
   const r = await fetch('/sdapi/v1/txt2img', {method:'POST',
     headers:{'Content-Type':'application/json'}, body: JSON.stringify(body)});
   const out = await r.json();

@@ -344,11 +344,42 @@ class BasicTransformerBlock(nn.Module):
         self.attn2 = CrossAttention(dim, context_dim, heads)  # cross
         self.norm3 = FusedLayerNorm(dim)
         self.ff = nn.Sequential(GEGLU(dim, dim * 4), nn.Linear(dim * 4, dim))
+        # token merging ratio of the self-attention (0: off, the unmerged
+        # path). The pipeline sets it on the level-0 blocks only.
+        self.tome_ratio = 0.0
 
-    def forward(self, x, context):
+    # token merging on the GPU: True runs the tome.hip kernels (match, merge,
+    # gathered add+LN); False keeps the torch-composed route (A/B timing,
+    # comparison tests). The CPU takes the torch route either way.
+    tome_native = True
+
+    def _tome_plan(self, x, hw):
+        """The merge plan of block input x (the metric, before norm1)."""
+        h, w = hw
+        r = ops.tome_merge_count(h, w, self.tome_ratio)
+        if r == 0:
+            return None
+        if self.tome_native or not x.is_cuda:
+            node_max, node_idx = ops.tome_match(x, h, w)
+        else:
+            node_max, node_idx = ops.tome_match(x.float(), h, w)
+        return ops.tome_plan(node_max, node_idx, h, w, r)
+
+    def forward(self, x, context, hw=None):
         from .layers import _fp32_cached
 
-        h = self.attn1(self.norm1(x))
+        plan = None
+        if self.tome_ratio > 0.0 and hw is not None:
+            plan = self._tome_plan(x, hw)
+        gather = None
+        if plan is None:
+            h = self.attn1(self.norm1(x))
+        elif self.tome_native or not x.is_cuda:
+            h = self.attn1(ops.tome_merge(self.norm1(x), plan))
+            gather = plan.slot  # the unmerge rides the add+LN's residual read
+        else:
+            h = self.attn1(ops.tome_merge(self.norm1(x), plan, native=False))
+            h = ops.tome_unmerge(h, plan, native=False)
         if x.is_cuda:
             w2, b2 = _fp32_cached(self.norm2)
             w3, b3 = _fp32_cached(self.norm3)
@@ -356,7 +387,7 @@ class BasicTransformerBlock(nn.Module):
             w2, b2 = self.norm2.weight, self.norm2.bias
             w3, b3 = self.norm3.weight, self.norm3.bias
         # fused residual-add + pre-norm (one HBM round trip saved per hop)
-        x, n2 = ops.add_layer_norm(x, h, w2, b2, self.norm2.eps)
+        x, n2 = ops.add_layer_norm(x, h, w2, b2, self.norm2.eps, gather=gather)
         h = self.attn2(n2, context)
         x, n3 = ops.add_layer_norm(x, h, w3, b3, self.norm3.eps)
         return x + self.ff(n3)
@@ -382,7 +413,7 @@ class SpatialTransformer(nn.Module):
         x = x.permute(0, 2, 3, 1).reshape(b, h * w, c)
         x = self.proj_in(x)
         for blk in self.blocks:
-            x = blk(x, context)
+            x = blk(x, context, (h, w))
         x = self.proj_out(x)
         x = x.reshape(b, h, w, c).permute(0, 3, 1, 2)
         # the add also emits the next ResBlock's GroupNorm partials
@@ -446,6 +477,10 @@ class UNetModel(nn.Module):
         self.conv_in = SDConv2d(cfg.in_channels, ch, 3, padding=1)
 
         self.down = nn.ModuleList()
+        # the SpatialTransformers at full latent resolution (token merging
+        # applies there only); a plain list, the modules are registered below
+        level0: List[nn.Module] = []
+        self._level0 = level0
         skip_chs = [ch]
         cur = ch
         levels = len(cfg.channel_mult)
@@ -464,6 +499,8 @@ class UNetModel(nn.Module):
                             cfg.groups,
                         )
                     )
+                    if lvl == 0:
+                        level0.append(mods[-1])
                 self.down.append(_Seq(*mods))
                 skip_chs.append(cur)
             if lvl != levels - 1:
@@ -494,12 +531,24 @@ class UNetModel(nn.Module):
                             cfg.groups,
                         )
                     )
+                    if lvl == 0:
+                        level0.append(mods[-1])
                 if lvl != 0 and i == cfg.num_res_blocks:
                     mods.append(Upsample(cur))
                 self.up.append(_Seq(*mods))
 
         self.norm_out = FusedGroupNorm(cur, cfg.groups, silu=True)
         self.conv_out = SDConv2d(cur, cfg.out_channels, 3, padding=1)
+
+    def level0_blocks(self) -> List["BasicTransformerBlock"]:
+        """The transformer blocks that see the full latent grid (level 0,
+        down and up path). Empty for SDXL, which has none there."""
+        return [blk for st in self._level0 for blk in st.blocks]
+
+    def set_tome_ratio(self, ratio: float) -> None:
+        """Token merging ratio of the level-0 self-attentions (0 = off)."""
+        for blk in self.level0_blocks():
+            blk.tome_ratio = float(ratio)
 
     def forward(
         self,

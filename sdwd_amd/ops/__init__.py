@@ -139,14 +139,254 @@ def layer_norm(
     ).to(x.dtype)
 
 
-def add_layer_norm(x, res, weight, bias, eps: float = 1e-5):
-    """(x + res, LayerNorm(x + res)) in one kernel (transformer residuals)."""
+def add_layer_norm(x, res, weight, bias, eps: float = 1e-5, gather=None):
+    """(x + res, LayerNorm(x + res)) in one kernel (transformer residuals).
+
+    gather (token merging): an int32 [B, N] table, plan.slot. res is then
+    the merged sequence [B, M, D] and row t of x adds res[b, gather[b, t]]:
+    the unmerge folded into the add, so the unmerged tensor never exists."""
     if x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] % 8 == 0 \
             and x.shape[-1] <= 1536:
-        out = ext().add_layer_norm(x, res, weight, bias, eps)
+        if gather is not None:
+            out = ext().add_layer_norm_gather(
+                x, res, weight, bias, eps, gather.contiguous()
+            )
+        else:
+            out = ext().add_layer_norm(x, res, weight, bias, eps)
         return out[0], out[1]
+    if gather is not None:
+        res = _tome_gather_rows(res, gather)
     s = (x.float() + res.float()).to(x.dtype)
     return s, layer_norm(s, weight, bias, eps)
+
+
+# ---------------------------------------------------------------------------
+# token merging (ToMe) for the level-0 self-attention: 2x2 partition, cosine
+# match, plan, merge, unmerge. Kernels in ops/hip/tome.hip; every op has a
+# plain torch path (CPU route, oracle, and the composed GPU route for widths
+# and dtypes without a kernel). docs/kernels.md has the definition.
+# ---------------------------------------------------------------------------
+_TOME_PARTITIONS: dict = {}
+_TOME_NORM_FLOOR = 2.0 ** -80
+
+
+def tome_merge_count(h: int, w: int, ratio: float) -> int:
+    """r = min(Ns, int(N * ratio)): src tokens merged away per batch row."""
+    n = int(h) * int(w)
+    nd = (int(h) // 2) * (int(w) // 2)
+    if nd == 0:  # a one-token-wide grid has no dst to merge into
+        return 0
+    return max(0, min(n - nd, int(n * float(ratio))))
+
+
+def _tome_partition_all(h: int, w: int, device):
+    """(src_tok, dst_tok, inv): the int32 tables and the int64 inverse of the
+    permutation cat(src_tok, dst_tok), cached per (h, w, device)."""
+    h, w = int(h), int(w)
+    if h < 2 or w < 2:
+        raise ValueError(f"tome_partition: needs h, w >= 2 (got {h}x{w})")
+    device = torch.device(device)
+    key = (h, w, device)
+    hit = _TOME_PARTITIONS.get(key)
+    if hit is None:
+        yy = torch.arange(h)[:, None].expand(h, w)
+        xx = torch.arange(w)[None, :].expand(h, w)
+        is_dst = (
+            (yy % 2 == 0) & (xx % 2 == 0)
+            & (yy < 2 * (h // 2)) & (xx < 2 * (w // 2))
+        ).reshape(-1)
+        tok = torch.arange(h * w)
+        src, dst = tok[~is_dst], tok[is_dst]
+        inv = torch.empty(h * w, dtype=torch.int64)
+        inv[torch.cat([src, dst])] = tok
+        hit = (
+            src.to(torch.int32).to(device),
+            dst.to(torch.int32).to(device),
+            inv.to(device),
+        )
+        _TOME_PARTITIONS[key] = hit
+    return hit
+
+
+def tome_partition(h: int, w: int, device="cpu"):
+    """int32 tables (src_tok [Ns], dst_tok [Nd]) of the 2x2 partition of an
+    h x w token grid, ascending, cached per (h, w, device). Token (y, x) is
+    dst iff y and x are even and inside the 2*(h//2) x 2*(w//2) region."""
+    src, dst, _ = _tome_partition_all(h, w, device)
+    return src, dst
+
+
+def tome_match_supported(x: torch.Tensor) -> bool:
+    """True when tome_match runs tome_match_bf16_kernel on x: a bf16 GPU
+    tensor [B, N, C] of a width with an instantiation (C = 320)."""
+    return bool(
+        x.is_cuda and x.dim() == 3 and x.dtype == torch.bfloat16
+        and ext().tome_match_supported_width(x.shape[-1])
+    )
+
+
+def tome_match(x: torch.Tensor, h: int, w: int):
+    """(node_max fp32 [B, Ns], node_idx int32 [B, Ns]): for every src token
+    of x [B, h*w, C] its largest cosine score over the dst tokens of the same
+    batch row and the lowest dst index attaining it. 1/|v| is
+    rsqrt(max(sum v^2, 2^-80)).
+
+    GPU, tome_match_supported(x): tome_match_bf16_kernel, scores never
+    materialised. Other widths / dtypes on the GPU, and the CPU: fp32 bmm +
+    max (the CPU path is the oracle of the kernel)."""
+    if x.dim() != 3 or x.shape[1] != int(h) * int(w):
+        raise ValueError("tome_match: x must be [B, h*w, C]")
+    src, dst, _ = _tome_partition_all(h, w, x.device)
+    if tome_match_supported(x):
+        out = ext().tome_match(x.contiguous(), src, dst)
+        return out[0], out[1]
+    xf = x.float()
+    a = xf[:, src.long()]
+    b = xf[:, dst.long()]
+    rna = torch.rsqrt((a * a).sum(-1).clamp_min(_TOME_NORM_FLOOR))
+    rnb = torch.rsqrt((b * b).sum(-1).clamp_min(_TOME_NORM_FLOOR))
+    score = torch.bmm(a, b.transpose(1, 2)) * rnb[:, None, :]
+    mx = score.max(dim=-1).values
+    nd = score.shape[-1]
+    ar = torch.arange(nd, device=x.device)
+    idx = torch.where(score == mx[..., None], ar, nd).min(dim=-1).values
+    idx = idx.clamp_max(nd - 1)  # a NaN row matches nothing
+    return mx * rna, idx.to(torch.int32)
+
+
+class TomePlan:
+    """The integer side of one merge: int32 tensors on the data's device.
+    slot [B, N]: row of the merged sequence that token t reads back;
+    unm_tok [B, Ns-r]: unmerged src tokens, ascending; seg_start [B, Nd+1]
+    and members [B, r]: CSR of every dst's merged src tokens, ascending
+    token position inside a segment; dst_tok [Nd]."""
+
+    __slots__ = ("h", "w", "r", "slot", "unm_tok", "seg_start", "members",
+                 "dst_tok")
+
+    def __init__(self, h, w, r, slot, unm_tok, seg_start, members, dst_tok):
+        self.h, self.w, self.r = h, w, r
+        self.slot, self.unm_tok = slot, unm_tok
+        self.seg_start, self.members, self.dst_tok = seg_start, members, dst_tok
+
+    @property
+    def tokens(self) -> int:
+        return self.h * self.w
+
+    @property
+    def merged_tokens(self) -> int:
+        return self.h * self.w - self.r
+
+    def tensors(self):
+        return (self.slot, self.unm_tok, self.seg_start, self.members)
+
+
+def tome_plan(node_max, node_idx, h: int, w: int, r: int) -> TomePlan:
+    """Select the r src tokens with the largest node_max (ties to the lower
+    src position) and lay out the merge. Torch integer ops with static
+    shapes on node_max's device, the same on CPU and GPU: two stable sorts,
+    a cumsum, a searchsorted and scatters to unique (or discarded) targets.
+    No host sync, no atomics, so it captures into a hipGraph."""
+    src, dst, inv = _tome_partition_all(h, w, node_max.device)
+    ns, nd = src.numel(), dst.numel()
+    bsz = node_max.shape[0]
+    r = int(r)
+    if tuple(node_max.shape) != (bsz, ns) or tuple(node_idx.shape) != (bsz, ns):
+        raise ValueError(f"tome_plan: node_max/node_idx must be [B, {ns}]")
+    if not 0 <= r <= ns:
+        raise ValueError(f"tome_plan: r must lie in [0, {ns}] (got {r})")
+    dev = node_max.device
+    nu = ns - r
+    pos = torch.arange(ns, device=dev)
+    order = torch.sort(
+        node_max.float(), dim=1, descending=True, stable=True
+    ).indices
+    rank = torch.empty_like(order)
+    rank.scatter_(1, order, pos[None].expand(bsz, ns))
+    merged = rank < r                                     # [B, Ns]
+    didx = node_idx.long().clamp(0, nd - 1)
+    # unmerged src tokens keep their order: slot = rank among the unmerged
+    urank = torch.cumsum((~merged).to(torch.int64), dim=1) - 1
+    slot_src = torch.where(merged, nu + didx, urank)
+    slot_dst = (nu + torch.arange(nd, device=dev))[None].expand(bsz, nd)
+    slot = torch.cat([slot_src, slot_dst], dim=1)[:, inv]
+    # unm_tok: every unmerged src writes its own cell; the merged ones all
+    # land in a spare cell that is cut off
+    buf = torch.empty(bsz, nu + 1, dtype=torch.int64, device=dev)
+    buf.scatter_(
+        1, torch.where(merged, nu, urank), src.long()[None].expand(bsz, ns)
+    )
+    unm_tok = buf[:, :nu]
+    # CSR of members per dst: stable sort of dst-or-sentinel keys in token
+    # order, segment starts by binary search
+    keys = torch.where(merged, didx, nd)
+    skeys, perm = torch.sort(keys, dim=1, stable=True)
+    members = src.long()[perm[:, :r]]
+    bounds = torch.arange(nd + 1, device=dev)[None].expand(bsz, nd + 1)
+    seg_start = torch.searchsorted(skeys.contiguous(), bounds.contiguous())
+    i32 = torch.int32
+    return TomePlan(
+        int(h), int(w), r, slot.to(i32).contiguous(),
+        unm_tok.to(i32).contiguous(), seg_start.to(i32).contiguous(),
+        members.to(i32).contiguous(), dst,
+    )
+
+
+def _tome_native_rows(x: torch.Tensor) -> bool:
+    return bool(
+        x.is_cuda and x.dim() == 3 and x.dtype == torch.bfloat16
+        and x.shape[-1] % 8 == 0
+    )
+
+
+def _tome_gather_rows(y: torch.Tensor, slot: torch.Tensor) -> torch.Tensor:
+    idx = slot.long()[..., None].expand(-1, -1, y.shape[-1])
+    return torch.gather(y, 1, idx)
+
+
+def tome_merge(x: torch.Tensor, plan: TomePlan, native: bool = True):
+    """x [B, N, C] -> [B, N-r, C]: the unmerged src tokens in ascending
+    position, then the dst tokens, each (dst + its members) / (1 + count),
+    summed in fp32 dst first then members in CSR order, one true division,
+    one rounding to x's dtype.
+
+    GPU bf16 with C % 8 == 0: tome_merge_bf16_kernel. Otherwise (and with
+    native=False, the composed route for comparisons) the same arithmetic
+    in torch, one step per member rank; its loop bound is the largest
+    segment, read on the host, so that route does not capture."""
+    bsz, n, c = x.shape
+    if n != plan.tokens:
+        raise ValueError("tome_merge: x and plan disagree on the token count")
+    if native and _tome_native_rows(x):
+        return ext().tome_merge(
+            x.contiguous(), plan.dst_tok, plan.unm_tok, plan.seg_start,
+            plan.members,
+        )
+    seg = plan.seg_start.long()
+    start, stop = seg[:, :-1], seg[:, 1:]
+    count = stop - start
+    members = plan.members.long()
+    acc = x[:, plan.dst_tok.long()].float()
+    depth = int(count.max()) if plan.r > 0 else 0
+    for k in range(depth):
+        live = (k < count)
+        at = (start + k).clamp_max(max(plan.r - 1, 0))
+        tok = torch.gather(members, 1, at)
+        rows = _tome_gather_rows(x, tok).float()
+        acc = torch.where(live[..., None], acc + rows, acc)
+    dstrows = (acc / (1 + count).float()[..., None]).to(x.dtype)
+    unm = _tome_gather_rows(x, plan.unm_tok)
+    return torch.cat([unm, dstrows], dim=1)
+
+
+def tome_unmerge(y: torch.Tensor, plan: TomePlan, native: bool = True):
+    """y [B, N-r, C] -> [B, N, C]: every original token gets the row of its
+    slot. GPU bf16, C % 8 == 0: tome_unmerge_bf16_kernel; else a gather."""
+    if y.shape[1] != plan.merged_tokens:
+        raise ValueError("tome_unmerge: y and plan disagree on the row count")
+    if native and _tome_native_rows(y):
+        return ext().tome_unmerge(y.contiguous(), plan.slot)
+    return _tome_gather_rows(y, plan.slot)
 
 
 # ---------------------------------------------------------------------------

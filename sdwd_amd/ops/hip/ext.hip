@@ -19,6 +19,7 @@ static inline hipStream_t cur_stream() {
 #include "conv.hip"
 #include "conv_small.hip"
 #include "rng.hip"
+#include "tome.hip"
 
 #define CHECK_IN(x)                                                     \
   TORCH_CHECK(x.is_cuda(), #x " must be on GPU");                        \
@@ -350,8 +351,166 @@ std::vector<torch::Tensor> add_layer_norm(torch::Tensor x, torch::Tensor r,
                      (const __hip_bfloat16 *)rc.data_ptr(),
                      wf.data_ptr<float>(), bf.data_ptr<float>(),
                      (__hip_bfloat16 *)out_sum.data_ptr(),
-                     (__hip_bfloat16 *)out_ln.data_ptr(), R, D, (float)eps);
+                     (__hip_bfloat16 *)out_ln.data_ptr(), R, D, (float)eps,
+                     (const int *)nullptr, 0, 0);
   return {out_sum, out_ln};
+}
+
+static void check_tome_table(const torch::Tensor &t, const torch::Tensor &x,
+                             const char *name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == x.device() &&
+                  t.scalar_type() == torch::kInt && t.is_contiguous(),
+              "tome: ", name, " must be a contiguous int32 tensor on x's device");
+}
+
+// add_layer_norm with token merging's unmerge folded in: x [B,N,D], r
+// [B,M,D], slot int32 [B,N]; row t adds r[b, slot[b,t]]
+std::vector<torch::Tensor> add_layer_norm_gather(torch::Tensor x,
+                                                 torch::Tensor r,
+                                                 torch::Tensor w,
+                                                 torch::Tensor b, double eps,
+                                                 torch::Tensor slot) {
+  TORCH_CHECK(x.dim() == 3 && r.dim() == 3, "add_layer_norm: gather takes "
+                                            "x [B,N,D] and r [B,M,D]");
+  auto xc = x.contiguous();
+  auto rc = r.contiguous();
+  const int D = xc.size(-1);
+  const long B = xc.size(0), N = xc.size(1), M = rc.size(1);
+  TORCH_CHECK(xc.scalar_type() == torch::kBFloat16 && D % 8 == 0 &&
+                  D <= 1536,
+              "add_layer_norm: bf16, D%8==0, D<=1536");
+  TORCH_CHECK(xc.is_cuda() && rc.scalar_type() == torch::kBFloat16 &&
+                  rc.size(0) == B && rc.size(2) == D && M >= 1 &&
+                  rc.device() == xc.device(),
+              "add_layer_norm: r must be a bf16 [B,M,D] next to x");
+  check_tome_table(slot, xc, "slot");
+  TORCH_CHECK(slot.numel() == B * N, "add_layer_norm: slot must be [B,N]");
+  TORCH_CHECK(N < (1L << 31) && M < (1L << 31), "add_layer_norm: N, M < 2^31");
+  auto wf = f32_vec_aligned(w);
+  auto bf = f32_vec_aligned(b);
+  TORCH_CHECK(wf.numel() == D && bf.numel() == D, "add_layer_norm: w/b size");
+  auto out_sum = torch::empty_like(xc);
+  auto out_ln = torch::empty_like(xc);
+  const long R = B * N;
+  if (R == 0) return {out_sum, out_ln};
+  dim3 grid((unsigned)((R + 3) / 4)), block(256);
+  auto kern = D <= 512    ? add_layer_norm_bf16_kernel<1, true>
+              : D <= 1024 ? add_layer_norm_bf16_kernel<2, true>
+                          : add_layer_norm_bf16_kernel<3, true>;
+  hipLaunchKernelGGL(kern, grid, block, 0, cur_stream(),
+                     (const __hip_bfloat16 *)xc.data_ptr(),
+                     (const __hip_bfloat16 *)rc.data_ptr(),
+                     wf.data_ptr<float>(), bf.data_ptr<float>(),
+                     (__hip_bfloat16 *)out_sum.data_ptr(),
+                     (__hip_bfloat16 *)out_ln.data_ptr(), R, D, (float)eps,
+                     (const int *)slot.data_ptr(), (int)N, (int)M);
+  return {out_sum, out_ln};
+}
+
+// ---------------------------------------------------------------------------
+// token merging (tome.hip)
+// ---------------------------------------------------------------------------
+bool tome_match_supported_width(long c) { return c == 320; }
+
+// x bf16 [B,N,C] contiguous; src_tok [Ns], dst_tok [Nd] int32 ->
+// (node_max fp32 [B,Ns], node_idx int32 [B,Ns])
+std::vector<torch::Tensor> tome_match(torch::Tensor x, torch::Tensor src_tok,
+                                      torch::Tensor dst_tok) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 3 && x.is_contiguous() &&
+                  x.scalar_type() == torch::kBFloat16,
+              "tome_match: x must be a contiguous bf16 [B,N,C] GPU tensor");
+  const long B = x.size(0), N = x.size(1), C = x.size(2);
+  TORCH_CHECK(tome_match_supported_width(C),
+              "tome_match: no kernel for C=", C);
+  check_tome_table(src_tok, x, "src_tok");
+  check_tome_table(dst_tok, x, "dst_tok");
+  const long Ns = src_tok.numel(), Nd = dst_tok.numel();
+  TORCH_CHECK(Ns >= 1 && Nd >= 1 && Ns + Nd == N && N < (1L << 31),
+              "tome_match: src_tok and dst_tok must partition the N tokens");
+  TORCH_CHECK(B <= 65535, "tome_match: B <= 65535");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "tome_match: x must be 16 B aligned");
+  auto fopt = x.options().dtype(torch::kFloat);
+  auto rn = torch::empty({B, N}, fopt);
+  auto node_max = torch::empty({B, Ns}, fopt);
+  auto node_idx = torch::empty({B, Ns}, x.options().dtype(torch::kInt));
+  if (B == 0) return {node_max, node_idx};
+  hipLaunchKernelGGL(tome_rnorm_bf16_kernel,
+                     dim3((unsigned)((B * N + 3) / 4)), dim3(256), 0,
+                     cur_stream(), (const __hip_bfloat16 *)x.data_ptr(),
+                     rn.data_ptr<float>(), B * N, (int)C);
+  hipLaunchKernelGGL(tome_match_bf16_kernel<320>,
+                     dim3((unsigned)((Ns + 127) / 128), (unsigned)B),
+                     dim3(256), 0, cur_stream(),
+                     (const __hip_bfloat16 *)x.data_ptr(),
+                     rn.data_ptr<float>(), (const int *)src_tok.data_ptr(),
+                     (const int *)dst_tok.data_ptr(),
+                     node_max.data_ptr<float>(), (int *)node_idx.data_ptr(),
+                     (int)N, (int)Ns, (int)Nd);
+  return {node_max, node_idx};
+}
+
+// x bf16 [B,N,C]; dst_tok [Nd]; unm_tok [B,Nu]; seg_start [B,Nd+1];
+// members [B,r] -> [B, Nu+Nd, C]
+torch::Tensor tome_merge(torch::Tensor x, torch::Tensor dst_tok,
+                         torch::Tensor unm_tok, torch::Tensor seg_start,
+                         torch::Tensor members) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 3 && x.is_contiguous() &&
+                  x.scalar_type() == torch::kBFloat16 && x.size(2) % 8 == 0,
+              "tome_merge: x must be a contiguous bf16 [B,N,C], C%8==0");
+  const long B = x.size(0), N = x.size(1), C = x.size(2);
+  check_tome_table(dst_tok, x, "dst_tok");
+  check_tome_table(unm_tok, x, "unm_tok");
+  check_tome_table(seg_start, x, "seg_start");
+  check_tome_table(members, x, "members");
+  const long Nd = dst_tok.numel();
+  TORCH_CHECK(unm_tok.dim() == 2 && members.dim() == 2 &&
+                  seg_start.dim() == 2 && unm_tok.size(0) == B &&
+                  members.size(0) == B && seg_start.size(0) == B &&
+                  seg_start.size(1) == Nd + 1,
+              "tome_merge: table shapes");
+  const long Nu = unm_tok.size(1), r = members.size(1);
+  TORCH_CHECK(Nd >= 1 && Nu + r + Nd == N && N < (1L << 31),
+              "tome_merge: the tables must cover the N tokens");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "tome_merge: x must be 16 B aligned");
+  auto out = torch::empty({B, Nu + Nd, C}, x.options());
+  const long rows = B * (Nu + Nd);
+  if (rows == 0) return out;
+  hipLaunchKernelGGL(tome_merge_bf16_kernel, dim3((unsigned)((rows + 3) / 4)),
+                     dim3(256), 0, cur_stream(),
+                     (const __hip_bfloat16 *)x.data_ptr(),
+                     (const int *)dst_tok.data_ptr(),
+                     (const int *)unm_tok.data_ptr(),
+                     (const int *)seg_start.data_ptr(),
+                     (const int *)members.data_ptr(),
+                     (__hip_bfloat16 *)out.data_ptr(), (int)B, (int)N,
+                     (int)Nu, (int)Nd, (int)r, (int)C);
+  return out;
+}
+
+// y bf16 [B,M,C]; slot int32 [B,N] -> [B,N,C]
+torch::Tensor tome_unmerge(torch::Tensor y, torch::Tensor slot) {
+  TORCH_CHECK(y.is_cuda() && y.dim() == 3 && y.is_contiguous() &&
+                  y.scalar_type() == torch::kBFloat16 && y.size(2) % 8 == 0,
+              "tome_unmerge: y must be a contiguous bf16 [B,M,C], C%8==0");
+  check_tome_table(slot, y, "slot");
+  const long B = y.size(0), M = y.size(1), C = y.size(2);
+  TORCH_CHECK(slot.dim() == 2 && slot.size(0) == B && M >= 1 &&
+                  M < (1L << 31) && slot.size(1) < (1L << 31),
+              "tome_unmerge: slot must be [B,N]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(y.data_ptr()) % 16 == 0,
+              "tome_unmerge: y must be 16 B aligned");
+  const long N = slot.size(1);
+  auto out = torch::empty({B, N, C}, y.options());
+  const long total = B * N * (C / 8);
+  if (total == 0) return out;
+  hipLaunchKernelGGL(tome_unmerge_bf16_kernel, dim3(ew_grid(total)), dim3(256),
+                     0, cur_stream(), (const __hip_bfloat16 *)y.data_ptr(),
+                     (const int *)slot.data_ptr(),
+                     (__hip_bfloat16 *)out.data_ptr(), B * N, (int)N, (int)M,
+                     (int)(C / 8));
+  return out;
 }
 
 // ---------------------------------------------------------------------------
@@ -627,6 +786,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("add_gn", &add_gn);
   m.def("layer_norm", &layer_norm);
   m.def("add_layer_norm", &add_layer_norm);
+  m.def("add_layer_norm_gather", &add_layer_norm_gather);
+  m.def("tome_match_supported_width", &tome_match_supported_width);
+  m.def("tome_match", &tome_match);
+  m.def("tome_merge", &tome_merge);
+  m.def("tome_unmerge", &tome_unmerge);
   m.def("row_softmax_", &row_softmax_);
   m.def("attention_fwd", &attention_fwd, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("scale"), py::arg("force") = 0);

@@ -377,20 +377,29 @@ __global__ __launch_bounds__(256) void gn_nhwc_norm_bf16(
 // normalise step (NV = 1, 2, 3 covers D <= 512, 1024, 1536). Both loops are
 // fully unrolled so the staged values have compile-time indices: no scratch.
 // w and b must be 16 B aligned.
+// GATHER (token merging's unmerge folded in): r is [B, M, D] and row t of
+// batch row bb adds r[bb, slot[bb*N + t]]; the entry is clamped to [0, M).
+// Without GATHER the three trailing arguments are unused.
 // ---------------------------------------------------------------------------
-template <int NV>
+template <int NV, bool GATHER = false>
 __global__ __launch_bounds__(256) void add_layer_norm_bf16_kernel(
     const __hip_bfloat16 *__restrict__ x, const __hip_bfloat16 *__restrict__ r,
     const float *__restrict__ w, const float *__restrict__ b,
     __hip_bfloat16 *__restrict__ out_sum, __hip_bfloat16 *__restrict__ out_ln,
-    long R, int D, float eps) {
+    long R, int D, float eps, const int *__restrict__ slot, int N, int M) {
   const int wid = threadIdx.x / WAVE;
   const int lane = threadIdx.x % WAVE;
   const long row = (long)blockIdx.x * 4 + wid;
   if (row >= R) return;
   const int nv = D / 8;  // D % 8 == 0 and nv <= NV * WAVE by dispatch
   const bf16x8 *xb = (const bf16x8 *)(x + row * D);
-  const bf16x8 *rb = (const bf16x8 *)(r + row * D);
+  long rrow = row;
+  if constexpr (GATHER) {
+    int s = slot[row];
+    s = s < 0 ? 0 : (s >= M ? M - 1 : s);
+    rrow = (row / N) * M + s;
+  }
+  const bf16x8 *rb = (const bf16x8 *)(r + rrow * D);
   bf16x8 *sb = (bf16x8 *)(out_sum + row * D);
   bf16x8 *lb = (bf16x8 *)(out_ln + row * D);
 

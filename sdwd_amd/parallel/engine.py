@@ -74,6 +74,10 @@ class GenerationRequest:
     seed_resize_from_h: int = 0
     eta_noise_seed_delta: int = 0
     randn_source: str = "CPU"  # "CPU" | "NV" (pipeline/noise.py)
+    # token merging ratios (see PipelineRequest for semantics); 0 = off
+    token_merging_ratio: float = 0.0
+    token_merging_ratio_img2img: float = 0.0
+    token_merging_ratio_hr: float = 0.0
     init_images: Optional[torch.Tensor] = None  # [B,H,W,3] uint8 (img2img)
     denoising_strength: float = 0.75
     mask_image: Optional[torch.Tensor] = None   # [H,W] uint8, 255=repaint
@@ -196,6 +200,9 @@ def _job_pipeline_request(
         seed_resize_from_h=gen.seed_resize_from_h,
         eta_noise_seed_delta=gen.eta_noise_seed_delta,
         randn_source=gen.randn_source,
+        token_merging_ratio=gen.token_merging_ratio,
+        token_merging_ratio_img2img=gen.token_merging_ratio_img2img,
+        token_merging_ratio_hr=gen.token_merging_ratio_hr,
         init_latents=init_latents,
         denoising_strength=gen.denoising_strength,
         mask_image=gen.mask_image,
@@ -1018,13 +1025,30 @@ class DistributedEngine(_EngineBase):
             plan = (
                 gen.model, self.world.make_jobs(gen.sched()),
                 gen.randn_source,
+                (
+                    gen.token_merging_ratio,
+                    gen.token_merging_ratio_img2img,
+                    gen.token_merging_ratio_hr,
+                ),
             )
         else:
             plan = None
-        model_name, jobs, randn_source = pg.broadcast_object(plan)
+        model_name, jobs, randn_source, tome = pg.broadcast_object(plan)
         if randn_source != gen.randn_source:
             # the noise source decides every image: rank 0's choice holds
             gen = replace_dc(gen, randn_source=randn_source)
+        if tome != (
+            gen.token_merging_ratio,
+            gen.token_merging_ratio_img2img,
+            gen.token_merging_ratio_hr,
+        ):
+            # so do the token merging ratios
+            gen = replace_dc(
+                gen,
+                token_merging_ratio=tome[0],
+                token_merging_ratio_img2img=tome[1],
+                token_merging_ratio_hr=tome[2],
+            )
         self.set_model(model_name)
         # per-worker checkpoint override (ref ui.py:161-171): purely local —
         # no collective weight sync, the deterministic registry (or the

@@ -166,6 +166,10 @@ AXIS_OPTIONS: List[AxisOption] = [
     AxisOption(
         "RNG source", "str", lambda g, v: replace(g, randn_source=str(v))
     ),
+    AxisOption(
+        "Token merging ratio", "float",
+        lambda g, v: replace(g, token_merging_ratio=float(v)),
+    ),
 ]
 
 _BY_NAME = {o.name.lower(): i for i, o in enumerate(AXIS_OPTIONS)}
@@ -181,6 +185,7 @@ _BY_NAME.update({
     "schedule": 14, "scheduler": 14,
     "eta noise seed delta": 19,
     "rng": 23, "randn_source": 23, "random number generator source": 23,
+    "token_merging_ratio": 24, "tome": 24,
 })
 
 

@@ -97,6 +97,13 @@ class PipelineRequest:
     refiner_model: str = ""
     refiner_switch_at: float = 0.8
     tiling: bool = False  # seamless tiles: wrap-around conv padding
+    # token merging (sdwui token_merging_ratio*): fraction of the tokens the
+    # level-0 self-attentions merge away, clamped to [0, 0.9]; 0 = off. The
+    # _hr / _img2img ratios apply to the hires pass / an img2img request and
+    # fall back to token_merging_ratio when 0.
+    token_merging_ratio: float = 0.0
+    token_merging_ratio_img2img: float = 0.0
+    token_merging_ratio_hr: float = 0.0
     # k-diffusion stochasticity (sdwui Sampler parameters section)
     s_churn: float = 0.0
     s_tmin: float = 0.0
@@ -244,6 +251,27 @@ def _upscale_latent(x: torch.Tensor, scale: float, upscaler: str,
     )
 
 
+def _clamp_tome_ratio(value) -> float:
+    return min(0.9, max(0.0, float(value or 0.0)))
+
+
+def token_merging_ratio_for(req, hr: bool = False) -> float:
+    """The token merging ratio in force for one pass of req (sdwui's
+    get_token_merging_ratio): the hires pass takes token_merging_ratio_hr,
+    an img2img request token_merging_ratio_img2img, each falling back to
+    token_merging_ratio when 0. Clamped to [0, 0.9]."""
+    base = _clamp_tome_ratio(getattr(req, "token_merging_ratio", 0.0))
+    if hr:
+        return _clamp_tome_ratio(
+            getattr(req, "token_merging_ratio_hr", 0.0)
+        ) or base
+    if getattr(req, "init_latents", None) is not None:
+        return _clamp_tome_ratio(
+            getattr(req, "token_merging_ratio_img2img", 0.0)
+        ) or base
+    return base
+
+
 def hires_active(enable_hr: bool, hr_scale: float, rx: int, ry: int) -> bool:
     """True when the hires second pass runs: sdwui's "resize to" mode
     (hr_resize_x/y set) enables the pass even with hr_scale<=1 (the UI
@@ -342,6 +370,7 @@ class StableDiffusionPipeline:
 
         self.lora = LoraManager(self.model.unet)
         self._tiling = False
+        self._tome_ratio = 0.0
         self._last_preview = None  # latest denoise-loop latents (preview)
         self._denoiser = GraphedDenoiser(
             lambda x, ts, ctx, y: self.model.unet(x, ts, ctx, y=y),
@@ -561,6 +590,22 @@ class StableDiffusionPipeline:
         )
         return lat.to(self.dtype)
 
+    def _set_tome_ratio(self, ratio: float) -> None:
+        """Token merging ratio of the UNet's level-0 self-attentions (the
+        ControlNet copies are not patched). Captured graphs baked the old
+        sequence length, so a change drops them, as the tiling switch
+        does."""
+        # the blocks are set every time: pipelines may share one model
+        self.model.unet.set_tome_ratio(ratio)
+        if ratio != self._tome_ratio:
+            self._denoiser.cache.clear()
+            # a running generation (the hires pass) still holds its
+            # whole-step wrapper: empty it too, not only the table
+            for graphed in self._wholestep_cache.values():
+                graphed.cache.clear()
+            self._wholestep_cache.clear()
+            self._tome_ratio = ratio
+
     # -- the denoise loop ----------------------------------------------------
     @torch.no_grad()
     def generate(
@@ -593,6 +638,8 @@ class StableDiffusionPipeline:
             self._denoiser.cache.clear()
             self._wholestep_cache.clear()
             self._tiling = req.tiling
+        tome_ratio = token_merging_ratio_for(req)
+        self._set_tome_ratio(tome_ratio)
         b = req.batch_size
         f = self.model.vae.cfg.downsample_factor
         lat_h, lat_w = req.height // f, req.width // f
@@ -1209,6 +1256,7 @@ class StableDiffusionPipeline:
                     crop_y // 2 : x.shape[2] - (crop_y - crop_y // 2),
                     crop_x // 2 : x.shape[3] - (crop_x - crop_x // 2),
                 ]
+            self._set_tome_ratio(token_merging_ratio_for(req, hr=True))
             hr_sampler = req.hr_sampler_name or req.sampler_name
             hsched = schedule_for(hr_sampler, hr_steps, req.scheduler)
             start = max(
@@ -1319,6 +1367,15 @@ class StableDiffusionPipeline:
             )
         if req.tiling:
             extra += ", Tiling: True"
+        if tome_ratio > 0:
+            extra += f", Token merging ratio: {tome_ratio}"
+        if hires_active(
+            req.enable_hr, req.hr_scale, req.hr_resize_x, req.hr_resize_y
+        ) and token_merging_ratio_for(req, hr=True) > 0:
+            extra += (
+                ", Token merging ratio hr: "
+                f"{token_merging_ratio_for(req, hr=True)}"
+            )
         prompt_of = (
             (lambda i: req.prompts[i]) if per_image else (lambda i: req.prompt)
         )

@@ -19,7 +19,12 @@ _RE_PARAM = re.compile(
 
 
 # infotext key -> request field it restores
-_REQUEST_FIELDS = {"RNG": "randn_source", "ENSD": "eta_noise_seed_delta"}
+_REQUEST_FIELDS = {
+    "RNG": "randn_source",
+    "ENSD": "eta_noise_seed_delta",
+    "Token merging ratio": "token_merging_ratio",
+    "Token merging ratio hr": "token_merging_ratio_hr",
+}
 
 
 def _unquote(v: str) -> str:
@@ -34,10 +39,11 @@ def parse_infotext(text: str) -> Dict[str, str]:
 
     Returns at least ``prompt`` and ``negative_prompt`` (possibly empty)
     plus one entry per ``Key: value`` pair from the final parameter line,
-    keys as written ("Steps", "CFG scale", "Worker Label", ...). The two
+    keys as written ("Steps", "CFG scale", "Worker Label", ...). The
     settings an image cannot be reproduced without are also returned under
-    their request field names: ``RNG`` as ``randn_source`` and ``ENSD`` as
-    ``eta_noise_seed_delta``.
+    their request field names: ``RNG`` as ``randn_source``, ``ENSD`` as
+    ``eta_noise_seed_delta``, ``Token merging ratio`` and ``Token merging
+    ratio hr`` as ``token_merging_ratio`` and ``token_merging_ratio_hr``.
     """
     lines = (text or "").split("\n")
     # the parameter line is the LAST line iff it parses as k:v pairs
