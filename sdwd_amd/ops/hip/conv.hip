@@ -25,11 +25,18 @@
 //  * FOLD instantiations run conv(nearest2x(x)) as four 2x2 sub-pixel convs
 //    on the source image with pre-summed weights (K = 4*Cin, not 9*Cin);
 //  * bias, per-(sample,channel) bias (time embedding) and the ResBlock
-//    residual add are fused into the epilogue.
+//    residual add are fused into the epilogue;
+//  * the epilogue of a full tile is vectorised (conv_epi_strip in
+//    conv_epilogue.h): operands fetched ahead of use, the rounded bf16 sub-tile transposed
+//    through wave-private LDS (free after the K loop), 16-byte stores of 8
+//    channels per lane. Edge tiles, cols % 8 != 0 and unaligned outputs keep
+//    the element-wise path; both compute the same bits. The bias is read as
+//    stored (bf16 or fp32).
 //
 // Requirements: Cin % 64 == 0 (every SD1.5/SDXL/VAE hot shape; the small-Cin
 // stem convs go to conv_small.hip), any Cout, stride 1 or 2, pad 1, kernel 3x3.
 #include "common.h"
+#include "conv_epilogue.h"
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -73,13 +80,14 @@ template <bool HAS_BIAS, bool HAS_RES, bool HAS_CB, int BN = 128,
 __launch_bounds__(256, 2) __global__ void conv3x3_nhwc_bf16_kernel(
     const __hip_bfloat16 *__restrict__ X,   // [N,H,W,Cin]
     const __hip_bfloat16 *__restrict__ Wt,  // [Cout,3,3,Cin]
-    const float *__restrict__ bias,         // [Cout] or null
+    const void *__restrict__ bias,          // [Cout] fp32 or bf16 (flags),
+                                            // or null
     const __hip_bfloat16 *__restrict__ Res, // [N,Ho,Wo,Cout] or null
     const __hip_bfloat16 *__restrict__ CB,  // [N,Cout] or null
     const __hip_bfloat16 *__restrict__ Zero,// >=16B of zeros
     __hip_bfloat16 *__restrict__ Y,         // [N,Ho,Wo,ldY] (+col offset)
     int Nn, int H, int W, int Cin, int Cout, int Ho, int Wo, int stride,
-    int ldY, float *__restrict__ GNP = nullptr, int wrap_h = 0,
+    int ldY, int flags, float *__restrict__ GNP = nullptr, int wrap_h = 0,
     int wrap_w = 0) {
   // GNP != null: emit per-(M-tile, channel) partial (sum, sumsq) of the
   // STORED values into GNP[mtile][2][ldY] so GroupNorm's stats pass can
@@ -299,47 +307,99 @@ __launch_bounds__(256, 2) __global__ void conv3x3_nhwc_bf16_kernel(
   }
 
   // ---- epilogue: bias, channel-bias, residual, store --------------------
+  // Full tiles of a launch the host cleared (flags & CONV_F_VEC) take the
+  // vector path, conv_epi_strip in conv_epilogue.h: operands fetched ahead of
+  // use, the bf16 sub-tile transposed through wave-private LDS, 16-byte
+  // stores. Edge tiles and unaligned launches keep the element-wise path.
+  // The arithmetic and the GroupNorm partial order are the same in both.
   const int r4 = (lane / 16) * 4;
   float gs[NJ], gq[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) gs[j] = gq[j] = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
+  const bool full =
+      (flags & CONV_F_VEC) && m0 + CONV_BM <= M && n0 + BN <= Cout;
+  if (full) {
+    // the wave's coordinates as scalars: bases stay in SGPRs and the loads
+    // and stores address as base + 32-bit lane offset
+    const int uw = __builtin_amdgcn_readfirstlane(wid);
+    const int uwm = (uw >> 1) * 64, uwn = (uw & 1) * (BN / 2);
+    float bv[NJ], cbv[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      const int co = n0 + wn + j * 16 + l16;
-      if (co >= Cout) continue;
-      const float bv = HAS_BIAS ? bias[co] : 0.0f;
+      bv[j] = HAS_BIAS ? conv_bias_at(bias, flags, n0 + uwn + j * 16 + l16)
+                       : 0.0f;
+      cbv[j] = 0.0f;
+    }
+    const unsigned HoWo = (unsigned)(Ho * Wo);  // host: fits
+    bool cb_one = true;
+    unsigned rem0 = 0;
+    const __hip_bfloat16 *cbw = nullptr;
+    if constexpr (HAS_CB) {
+      const long ni0 = m0 / (long)HoWo;  // block-uniform, once
+      const unsigned remb = (unsigned)(m0 - ni0 * (long)HoWo);
+      cb_one = remb + CONV_BM <= HoWo;
+      rem0 = remb + uwm;
+      cbw = CB + ni0 * (long)ldY + n0 + uwn;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        long m = m0 + wm + i * 16 + r4 + r;
-        if (m >= M) continue;
-        if constexpr (FOLD) {
-          // source pixel (n, i, j) -> output row (n, 2i+a, 2j+b); with
-          // q = n*H + i, n*Ho + 2i is 2q
-          const unsigned q = (unsigned)m / (unsigned)W;
-          const unsigned jw = (unsigned)m - q * (unsigned)W;
-          m = (long)(2 * q + fa) * Wo + 2 * jw + fb;
-        }
-        float v = acc[i][j][r] + bv;
-        if (HAS_CB) {
-          const int ni = (int)(m / ((long)Ho * Wo));
-          v += (float)CB[(long)ni * ldY + co];
-        }
-        if (HAS_RES) v += (float)Res[m * ldY + co];
-        const __hip_bfloat16 vb = f2bf(v);
-        Y[m * ldY + co] = vb;
-        if (GNP) {
-          const float vr = bf2f(vb);  // stats over the STORED values
-          gs[j] += vr;
-          gq[j] += vr * vr;
+      for (int j = 0; j < NJ; ++j) cbv[j] = (float)cbw[j * 16 + l16];
+    }
+    const long mw = m0 + uwm;
+    const __hip_bfloat16 *resw =
+        HAS_RES ? Res + mw * (long)ldY + n0 + uwn : nullptr;
+    __hip_bfloat16 *yw =
+        FOLD ? Y + n0 + uwn : Y + mw * (long)ldY + n0 + uwn;
+    // wave-private regions: disjoint from each other and from the
+    // GroupNorm staging below, so no barrier anywhere in here
+    char *wl = (char *)smem + wid * conv_epi_bytes<NJ>;
+    if (cb_one)
+      conv_epi_strip<HAS_RES, HAS_CB, true, FOLD, NJ, false>(
+          acc, bv, cbv, cbw, rem0, HoWo, resw, yw, mw, W, Wo, fa, fb,
+          (unsigned)ldY, wl, lane, gs, gq);
+    else
+      conv_epi_strip<HAS_RES, HAS_CB, false, FOLD, NJ, false>(
+          acc, bv, cbv, cbw, rem0, HoWo, resw, yw, mw, W, Wo, fa, fb,
+          (unsigned)ldY, wl, lane, gs, gq);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int co = n0 + wn + j * 16 + l16;
+        if (co >= Cout) continue;
+        const float bv = HAS_BIAS ? conv_bias_at(bias, flags, co) : 0.0f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          long m = m0 + wm + i * 16 + r4 + r;
+          if (m >= M) continue;
+          if constexpr (FOLD) {
+            // source pixel (n, i, j) -> output row (n, 2i+a, 2j+b); with
+            // q = n*H + i, n*Ho + 2i is 2q
+            const unsigned q = (unsigned)m / (unsigned)W;
+            const unsigned jw = (unsigned)m - q * (unsigned)W;
+            m = (long)(2 * q + fa) * Wo + 2 * jw + fb;
+          }
+          float v = acc[i][j][r] + bv;
+          if (HAS_CB) {
+            const int ni = (int)(m / ((long)Ho * Wo));
+            v += (float)CB[(long)ni * ldY + co];
+          }
+          if (HAS_RES) v += (float)Res[m * ldY + co];
+          const __hip_bfloat16 vb = f2bf(v);
+          Y[m * ldY + co] = vb;
+          if (GNP) {
+            const float vr = bf2f(vb);  // stats over the STORED values
+            gs[j] += vr;
+            gq[j] += vr * vr;
+          }
         }
       }
     }
   }
   if (GNP) {
-    // wave reduce: fold the 4 lane-quarters holding one column
-    float *lds = (float *)smem;  // staging LDS is free after the k-loop
+    // wave reduce: fold the 4 lane-quarters holding one column. Staged past
+    // the four wave-private epilogue regions, which other waves may still
+    // be transposing through (the staging LDS is free after the k-loop)
+    float *lds = (float *)((char *)smem + 4 * conv_epi_bytes<4>);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
 #pragma unroll
@@ -453,15 +513,31 @@ static dim3 conv_grid(long col_tiles, long mtiles) {
 
 // What the plain and the fused-upsample entry share: checks, output and
 // GroupNorm-partial allocation, and the operand pointers. The tensors are
-// members so the fp32 bias / bf16 chan-bias copies outlive the launch call.
+// members so a converted bias / bf16 chan-bias copy outlives the launch call.
+// A contiguous bf16 or fp32 bias is read by the kernels as it is stored.
 struct ConvArgs {
   int N, Cin, H, W, Cout, Ho, Wo;
   long M;
   torch::Tensor y, gnp, bias_f32, cb_bf16;
   const __hip_bfloat16 *x, *w, *res = nullptr, *cb = nullptr, *zero;
-  const float *bias = nullptr;
+  const char *bias = nullptr;
+  int bias_esize = 4;  // bytes per bias element: 4 (fp32) or 2 (bf16)
   __hip_bfloat16 *yp;
   float *gnp_ptr = nullptr;
+
+  // bias pointer of the launch that starts at output column co0
+  const void *bias_at(long co0) const {
+    return bias ? bias + co0 * bias_esize : nullptr;
+  }
+  // kernel `flags` of the launch that writes `cols` columns from co0: the
+  // vector epilogue stores 16 B = 8 channels per lane, so rows and the
+  // column offset must keep Y 16-byte aligned (Res and CB are read by
+  // element and need nothing)
+  int flags(long co0, long cols) const {
+    const bool vec = cols % 8 == 0 && Cout % 8 == 0 &&
+                     (reinterpret_cast<uintptr_t>(yp + co0) & 15) == 0;
+    return (vec ? CONV_F_VEC : 0) | (bias_esize == 2 ? CONV_F_BIAS_BF16 : 0);
+  }
 
   // x: [N,C,H,W] channels_last; w_prep: [Cout,3,3,Cin] contiguous
   ConvArgs(const torch::Tensor &xt, const torch::Tensor &w_prep,
@@ -482,9 +558,21 @@ struct ConvArgs {
     w = (const __hip_bfloat16 *)w_prep.data_ptr();
     yp = (__hip_bfloat16 *)y.data_ptr();
     zero = zero_page_for(xt);
+    // the vector epilogue's 32-bit offsets: up to 256 rows of ldY elements
+    // within a tile, and a row's index within its image
+    TORCH_CHECK(Cout < (1 << 20), "conv3x3: too many output channels");
+    TORCH_CHECK((long)Ho * Wo < (1L << 30), "conv3x3: output image too large");
     if (bias_t.has_value()) {
-      bias_f32 = bias_t->to(torch::kFloat).contiguous();
-      bias = bias_f32.data_ptr<float>();
+      TORCH_CHECK(bias_t->numel() == Cout, "conv3x3: bias must be [Cout]");
+      const auto bt = bias_t->scalar_type();
+      if ((bt == torch::kBFloat16 || bt == torch::kFloat) &&
+          bias_t->is_contiguous()) {
+        bias_f32 = *bias_t;  // no copy: the kernels read either type
+        bias_esize = bt == torch::kBFloat16 ? 2 : 4;
+      } else {
+        bias_f32 = bias_t->to(torch::kFloat).contiguous();
+      }
+      bias = (const char *)bias_f32.data_ptr();
     }
     if (residual.has_value()) {
       TORCH_CHECK(
@@ -537,9 +625,9 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> conv3x3_nhwc(
               (conv3x3_v4_kernel<decltype(B)::value, decltype(R)::value,
                                  decltype(C)::value, decltype(WR)::value>),
               conv_grid(cols / 256, (a.M + V4_BM - 1) / V4_BM), dim3(512), 0,
-              stream, a.x, a.w, a.bias, a.res, a.cb, a.zero, a.yp, a.N, a.H,
-              a.W, a.Cin, cols, a.Cout, a.Ho, a.Wo, (int)stride, a.gnp_ptr,
-              (int)wrap_h, (int)wrap_w);
+              stream, a.x, a.w, a.bias_at(0), a.res, a.cb, a.zero, a.yp, a.N,
+              a.H, a.W, a.Cin, cols, a.Cout, a.Ho, a.Wo, (int)stride,
+              a.flags(0, cols), a.gnp_ptr, (int)wrap_h, (int)wrap_w);
         },
         a.bias != nullptr, a.res != nullptr, a.cb != nullptr, wrap);
   }
@@ -557,11 +645,11 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> conv3x3_nhwc(
               conv_grid((cols + BN - 1) / BN,
                         (a.M + CONV_BM - 1) / CONV_BM),
               dim3(256), 0, stream, a.x, a.w + co0 * 9 * a.Cin,
-              a.bias ? a.bias + co0 : nullptr, a.res ? a.res + co0 : nullptr,
+              a.bias_at(co0), a.res ? a.res + co0 : nullptr,
               a.cb ? a.cb + co0 : nullptr, a.zero, a.yp + co0, a.N, a.H, a.W,
               a.Cin, cols, a.Ho, a.Wo, (int)stride, a.Cout,
-              a.gnp_ptr ? a.gnp_ptr + co0 : nullptr, (int)wrap_h,
-              (int)wrap_w);
+              a.flags(co0, cols), a.gnp_ptr ? a.gnp_ptr + co0 : nullptr,
+              (int)wrap_h, (int)wrap_w);
         },
         a.bias != nullptr, a.res != nullptr, a.cb != nullptr, bn64, wrap);
   }
@@ -610,9 +698,10 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> ups2x_conv3x3(
                                         true>),
               conv_grid((a.Cout + CONV_BN - 1) / CONV_BN,
                         4 * ((Mp + CONV_BM - 1) / CONV_BM)),
-              dim3(256), 0, stream, a.x, wf, a.bias, a.res, a.cb, a.zero,
-              a.yp, a.N, a.H, a.W, a.Cin, a.Cout, a.Ho, a.Wo, 1, a.Cout,
-              a.gnp_ptr, (int)wrap_h, (int)wrap_w);
+              dim3(256), 0, stream, a.x, wf, a.bias_at(0), a.res, a.cb,
+              a.zero, a.yp, a.N, a.H, a.W, a.Cin, a.Cout, a.Ho, a.Wo, 1,
+              a.Cout, a.flags(0, a.Cout), a.gnp_ptr, (int)wrap_h,
+              (int)wrap_w);
         },
         a.bias != nullptr, wrap_h || wrap_w);
     if (collect_gn && !epi_gn && ((long)a.Ho * a.Wo) % 128 == 0 &&
@@ -629,9 +718,9 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> ups2x_conv3x3(
                                       true, decltype(WR)::value>),
             conv_grid((a.Cout + CONV_BN - 1) / CONV_BN,
                       (a.M + CONV_BM - 1) / CONV_BM),
-            dim3(256), 0, stream, a.x, a.w, a.bias, a.res, a.cb, a.zero,
-            a.yp, a.N, a.H, a.W, a.Cin, a.Cout, a.Ho, a.Wo, 1, a.Cout,
-            a.gnp_ptr, (int)wrap_h, (int)wrap_w);
+            dim3(256), 0, stream, a.x, a.w, a.bias_at(0), a.res, a.cb,
+            a.zero, a.yp, a.N, a.H, a.W, a.Cin, a.Cout, a.Ho, a.Wo, 1,
+            a.Cout, a.flags(0, a.Cout), a.gnp_ptr, (int)wrap_h, (int)wrap_w);
       },
       a.bias != nullptr, wrap_h || wrap_w);
   return a.result();

@@ -13,11 +13,16 @@
 //    hipcc's own lgkm counting orders the ds_read->MFMA chain.
 //  * LDS rows are 128 B; the 8 16-B chunks XOR-swizzled by (row>>1)&7 on
 //    the glds SOURCE address (rule 21) - b128 fragment reads conflict-free.
-//  * bias / per-sample channel bias / residual fused in the epilogue.
+//  * bias / per-sample channel bias / residual fused in the epilogue. Full
+//    tiles take the vector epilogue (conv_epi_strip in conv_epilogue.h, shared with the
+//    v2 kernel): two 64-row strips per wave through 9 KiB of wave-private
+//    LDS each, 16-byte stores; residual loads run one fragment row ahead.
+//    Edge tiles keep the element-wise path.
 //
 // Covers full 256-column tiles only; the host launches the v2 kernel on
 // the Cout remainder (Cout=320 -> 256 here + 64 there).
 #include "common.h"
+#include "conv_epilogue.h"
 
 // XOR-permute the 8 16-byte chunks of a 128-byte LDS row (shared with the
 // v2 kernel in conv.hip): b128 fragment reads stay bank-conflict-free.
@@ -35,13 +40,14 @@ template <bool HAS_BIAS, bool HAS_RES, bool HAS_CB, bool WRAP = false>
 __launch_bounds__(512, 2) __global__ void conv3x3_v4_kernel(
     const __hip_bfloat16 *__restrict__ X,   // [N,H,W,Cin]
     const __hip_bfloat16 *__restrict__ Wt,  // [Cout,3,3,Cin] (+col offset)
-    const float *__restrict__ bias,         // [cols] or null (+col offset)
+    const void *__restrict__ bias,          // [cols] fp32 or bf16 (flags), or
+                                            // null (+col offset)
     const __hip_bfloat16 *__restrict__ Res, // [M,ldY] or null (+col offset)
     const __hip_bfloat16 *__restrict__ CB,  // [N,ldY] or null (+col offset)
     const __hip_bfloat16 *__restrict__ Zero,
     __hip_bfloat16 *__restrict__ Y,         // [M,ldY] (+col offset)
     int Nn, int H, int W, int Cin, int Cols, int ldY, int Ho, int Wo,
-    int stride, float *__restrict__ GNP = nullptr, int wrap_h = 0,
+    int stride, int flags, float *__restrict__ GNP = nullptr, int wrap_h = 0,
     int wrap_w = 0) {
   // GNP: per-(M-tile, channel) partial (sum, sumsq) of the stored values
   // (see conv.hip - lets GroupNorm skip its full-tensor stats read).
@@ -216,40 +222,93 @@ __launch_bounds__(512, 2) __global__ void conv3x3_v4_kernel(
     }
   }
 
-  // epilogue
+  // epilogue: full tiles of a launch the host cleared take the vector
+  // path (conv_epi_strip, two 64-row strips per wave); edge tiles and
+  // unaligned launches keep the element-wise one. Same arithmetic in both.
   const int r4 = (lane / 16) * 4;
   float gs[4], gq[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) gs[j] = gq[j] = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
+  const bool full =
+      (flags & CONV_F_VEC) && m0 + V4_BM <= M && n0 + V4_BN <= Cols;
+  if (full) {
+    // the wave's coordinates as scalars: bases stay in SGPRs and the loads
+    // and stores address as base + 32-bit lane offset
+    const int uw = __builtin_amdgcn_readfirstlane(wid);
+    const int uwm = (uw >> 2) * 128, uwn = (uw & 3) * 64;
+    float bv[4], cbv[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int co = n0 + wn + (j >> 1) * 32 + (j & 1) * 16 + l16;
-      if (co >= Cols) continue;
-      const float bv = HAS_BIAS ? bias[co] : 0.0f;
+      bv[j] = HAS_BIAS ? conv_bias_at(bias, flags, n0 + uwn + j * 16 + l16)
+                       : 0.0f;
+      cbv[j] = 0.0f;
+    }
+    const unsigned HoWo = (unsigned)(Ho * Wo);  // host: fits
+    bool cb_one = true;
+    unsigned remb = 0;
+    const __hip_bfloat16 *cbw = nullptr;
+    if constexpr (HAS_CB) {
+      const long ni0 = m0 / (long)HoWo;  // block-uniform, once
+      remb = (unsigned)(m0 - ni0 * (long)HoWo);
+      cb_one = remb + V4_BM <= HoWo;
+      cbw = CB + ni0 * (long)ldY + n0 + uwn;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long m = m0 + wm + (i >> 2) * 64 + (i & 3) * 16 + r4 + r;
-        if (m >= M) continue;
-        float v = acc[i][j][r] + bv;
-        if (HAS_CB) {
-          const int ni = (int)(m / ((long)Ho * Wo));
-          v += (float)CB[(long)ni * ldY + co];
-        }
-        if (HAS_RES) v += (float)Res[m * ldY + co];
-        const __hip_bfloat16 vb = f2bf(v);
-        Y[m * ldY + co] = vb;
-        if (GNP) {
-          const float vr = bf2f(vb);
-          gs[j] += vr;
-          gq[j] += vr * vr;
+      for (int j = 0; j < 4; ++j) cbv[j] = (float)cbw[j * 16 + l16];
+    }
+    // wave-private regions: disjoint from each other and from the
+    // GroupNorm staging below, so no barrier anywhere in here
+    char *wl = (char *)smem + wid * conv_epi_bytes<4>;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const long mw = m0 + uwm + s * 64;
+      const f32x4(&sa)[4][4] = *reinterpret_cast<const f32x4(*)[4][4]>(
+          &acc[s * 4]);
+      const __hip_bfloat16 *resw =
+          HAS_RES ? Res + mw * (long)ldY + n0 + uwn : nullptr;
+      __hip_bfloat16 *yw = Y + mw * (long)ldY + n0 + uwn;
+      const unsigned rem0 = remb + uwm + s * 64;
+      if (cb_one)
+        conv_epi_strip<HAS_RES, HAS_CB, true, false, 4, true>(
+            sa, bv, cbv, cbw, rem0, HoWo, resw, yw, mw, 0, 0, 0, 0,
+            (unsigned)ldY, wl, lane, gs, gq);
+      else
+        conv_epi_strip<HAS_RES, HAS_CB, false, false, 4, true>(
+            sa, bv, cbv, cbw, rem0, HoWo, resw, yw, mw, 0, 0, 0, 0,
+            (unsigned)ldY, wl, lane, gs, gq);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int co = n0 + wn + (j >> 1) * 32 + (j & 1) * 16 + l16;
+        if (co >= Cols) continue;
+        const float bv = HAS_BIAS ? conv_bias_at(bias, flags, co) : 0.0f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const long m = m0 + wm + (i >> 2) * 64 + (i & 3) * 16 + r4 + r;
+          if (m >= M) continue;
+          float v = acc[i][j][r] + bv;
+          if (HAS_CB) {
+            const int ni = (int)(m / ((long)Ho * Wo));
+            v += (float)CB[(long)ni * ldY + co];
+          }
+          if (HAS_RES) v += (float)Res[m * ldY + co];
+          const __hip_bfloat16 vb = f2bf(v);
+          Y[m * ldY + co] = vb;
+          if (GNP) {
+            const float vr = bf2f(vb);
+            gs[j] += vr;
+            gq[j] += vr * vr;
+          }
         }
       }
     }
   }
   if (GNP) {
-    float *lds = (float *)smem;  // free after the k-loop
+    // staged past the eight wave-private epilogue regions, which other
+    // waves may still be transposing through
+    float *lds = (float *)((char *)smem + 8 * conv_epi_bytes<4>);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
 #pragma unroll

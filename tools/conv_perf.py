@@ -8,6 +8,11 @@ before the kernels could wrap: F.pad(mode="circular") + F.conv2d.
 --ups times only the six fused upsample convs of the headline workload:
 the folded 2x2 sub-pixel kernel against the 9-tap kernel, alternating in
 one process, in ms and in TF/s on the FLOPs each kernel executes.
+
+--extras times each shape the three ways the UNet calls it (plain, with the
+residual, with the time-embedding bias and the GroupNorm partials), at Cin
+and 2 Cin, and fits time = a * K tiles + b. --dump DIR writes the outputs
+and partials of seeded inputs, to compare two builds bit for bit.
 """
 import argparse
 import json
@@ -44,7 +49,15 @@ ap.add_argument("--ups", action="store_true",
                 help="only the fused upsample convs: folded 2x2 sub-pixel "
                      "kernel vs the 9-tap kernel, alternating in this process")
 ap.add_argument("--rounds", type=int, default=7,
-                help="--ups: alternating rounds per shape")
+                help="--ups / --extras: alternating rounds per shape")
+ap.add_argument("--extras", action="store_true",
+                help="each of SHAPES plain, with residual, and with channel "
+                     "bias + collect_gn, at Cin and 2 Cin, with the "
+                     "time = a * K tiles + b fit")
+ap.add_argument("--dump", metavar="DIR",
+                help="write outputs and GroupNorm partials of seeded inputs "
+                     "(every SHAPES row and mode, every upsample conv) as "
+                     ".npy into DIR")
 args = ap.parse_args()
 
 
@@ -114,8 +127,123 @@ def ups_perf():
     print(json.dumps(res, indent=1))
 
 
+def extras_inputs(N, Ci, H, W, Co, s, seed):
+    """Seeded operands of one SHAPES row as the UNet passes them: bf16
+    bias, channels_last residual, bf16 [N, Cout] time-embedding bias."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+
+    def rnd(*shape):
+        return torch.randn(*shape, device="cuda", generator=g)
+
+    x = rnd(N, Ci, H, W).bfloat16()
+    xc = x.contiguous(memory_format=torch.channels_last)
+    w = (rnd(Co, Ci, 3, 3) * 0.02).bfloat16()
+    wp = w.permute(0, 2, 3, 1).contiguous()
+    b = rnd(Co).bfloat16()
+    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    res = rnd(N, Co, Ho, Wo).bfloat16().contiguous(
+        memory_format=torch.channels_last)
+    cb = rnd(N, Co).bfloat16()
+    return xc, wp, b, res, cb
+
+
+def extras_modes(xc, wp, b, res, cb, s):
+    """plain: conv + bias (+ partials for the next GroupNorm); res: the
+    ResBlock's conv2 with its skip; cb: conv1 with the time embedding."""
+    return {
+        "plain": lambda: ops.conv3x3(xc, wp, b, None, s),
+        "res": lambda: ops.conv3x3(xc, wp, b, res, s),
+        "cb": lambda: ops.conv3x3(xc, wp, b, None, s, chan_bias=cb,
+                                  collect_gn=True),
+    }
+
+
+def extras_perf():
+    """Per SHAPES row and mode: `rounds` timings (20 calls after 2 warm-up
+    calls each, modes alternating) at Cin and at 2 Cin, and the r07 fit
+    time = a * K tiles + b from the two medians (K tiles = 9 Cin / 64).
+    One JSON object; compare two builds by running this once per build in
+    alternating processes."""
+    res_all = {}
+    for (N, Ci, H, W, Co, s) in SHAPES:
+        row = {}
+        for mult in (1, 2):
+            ops_in = extras_inputs(N, Ci * mult, H, W, Co, s, 11)
+            modes = extras_modes(*ops_in, s)
+            ts = {k: [] for k in modes}
+            for _ in range(args.rounds):
+                for k, fn in modes.items():
+                    ts[k].append(t(fn, warm=2, it=20))
+            for k, v in ts.items():
+                v = sorted(v)
+                row.setdefault(k, {})[f"ms_x{mult}"] = {
+                    "med": round(v[len(v) // 2] * 1e3, 4),
+                    "min": round(v[0] * 1e3, 4),
+                    "max": round(v[-1] * 1e3, 4),
+                }
+            del ops_in, modes
+        for k, d in row.items():
+            k1 = 9 * Ci // 64
+            t1, t2 = d["ms_x1"]["med"], d["ms_x2"]["med"]
+            a = (t2 - t1) / k1
+            d["a_ms_per_ktile"] = round(a, 5)
+            d["b_fixed_ms"] = round(t1 - a * k1, 4)
+        res_all[f"{N}x{Ci}x{H}x{W}->{Co}/s{s}"] = row
+    print(json.dumps(res_all))
+
+
+def extras_dump(out_dir):
+    """Outputs and GroupNorm partials of seeded inputs as .npy (bf16 as its
+    int16 bit pattern), per SHAPES row, mode and upsample shape: two builds
+    compute the same iff the files are byte-equal. conv3x3_plan depends on
+    the row count, so each conv is dumped twice: whole at a small batch
+    (which the plan sends to the v2 kernel, mostly at BN = 64), and at the
+    timed batch, the kernels the timings run (v4, v2 at BN = 128), as every
+    1021st element of y plus all partials."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, y, step=1):
+        flat = y.permute(0, 2, 3, 1).reshape(-1).view(torch.int16)
+        np.save(os.path.join(out_dir, name + "_y.npy"),
+                flat[::step].cpu().numpy())
+        gnp = getattr(y, "_sdwd_gnp", None)
+        if gnp is not None:
+            np.save(os.path.join(out_dir, name + "_gnp.npy"),
+                    gnp[0].cpu().numpy())
+
+    def all_modes(name, ops_in, s, step):
+        for k, fn in extras_modes(*ops_in, s).items():
+            save(f"{name}_{k}", fn(), step)
+        xc, wp, b, res, cb = ops_in
+        save(f"{name}_all", ops.conv3x3(xc, wp, b, res, s, chan_bias=cb,
+                                        collect_gn=True), step)
+
+    for i, (N, Ci, H, W, Co, s) in enumerate(SHAPES):
+        n = max(1, min(N, 4, 65536 // (H * W)))
+        all_modes(f"conv{i}_n{n}", extras_inputs(n, Ci, H, W, Co, s, 100 + i),
+                  s, 1)
+        all_modes(f"conv{i}_n{N}", extras_inputs(N, Ci, H, W, Co, s, 300 + i),
+                  s, 1021)
+    for i, (N, Ci, H, W, Co) in enumerate(UPS_SHAPES):
+        n = max(1, min(N, 2, 16384 // (H * W)))
+        xc, wp, b, _, _ = extras_inputs(n, Ci, H, W, Co, 1, 200 + i)
+        save(f"ups{i}_fold", ops.ups2x_conv3x3(xc, wp, b, collect_gn=True))
+        save(f"ups{i}_tap9", ops.ups2x_conv3x3(xc, wp, b, collect_gn=True,
+                                               fold=False))
+    torch.cuda.synchronize()
+    print(json.dumps({"dumped": len(os.listdir(out_dir)), "dir": out_dir}))
+
+
 if args.ups:
     ups_perf()
+    sys.exit(0)
+if args.dump:
+    extras_dump(args.dump)
+    sys.exit(0)
+if args.extras:
+    extras_perf()
     sys.exit(0)
 
 out = {}
