@@ -127,6 +127,43 @@ def _tome_ratio(value) -> float:
     return min(0.9, max(0.0, ratio))
 
 
+# sdwui Hypertile options -> (GenerationRequest field, kind, default). The
+# swap size is accepted (host GUIs send every option) and treated as 1, the
+# VAE switch is accepted and ignored: docs/usage.md, "Hypertile".
+_HYPERTILE_OPTIONS = {
+    "hypertile_enable_unet": ("hypertile_unet", "bool", False),
+    "hypertile_enable_unet_secondpass": (
+        "hypertile_unet_secondpass", "bool", False,
+    ),
+    "hypertile_max_depth_unet": ("hypertile_max_depth", "depth", 3),
+    "hypertile_max_tile_unet": ("hypertile_max_tile", "tile", 256),
+    "hypertile_swap_size_unet": (None, "swap", 1),
+    "hypertile_enable_vae": (None, "bool", False),
+}
+_HYPERTILE_RANGE = {"depth": (0, 3), "tile": (0, 512), "swap": (1, 64)}
+
+
+def _hypertile_value(key: str, value):
+    """A validated Hypertile option; a value of the wrong type or outside
+    the host's slider range is a 422 naming the key."""
+    kind = _HYPERTILE_OPTIONS[key][1]
+    if kind == "bool":
+        if not isinstance(value, bool):
+            raise HTTPException(422, f"{key}: expected true or false, got "
+                                     f"{value!r}")
+        return value
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        raise HTTPException(422, f"{key}: expected an integer, got {value!r}")
+    if value != value:
+        raise HTTPException(422, f"{key}: NaN")
+    if isinstance(value, float) and not value.is_integer():  # inf too
+        raise HTTPException(422, f"{key}: expected an integer, got {value!r}")
+    lo, hi = _HYPERTILE_RANGE[kind]
+    if not lo <= value <= hi:
+        raise HTTPException(422, f"{key}: {int(value)} is outside {lo}..{hi}")
+    return int(value)
+
+
 class ServerState:
     def __init__(self, engine: LocalEngine):
         self.engine = engine
@@ -141,6 +178,8 @@ class ServerState:
         self.randn_source = "CPU"  # "CPU" | "NV" (pipeline/noise.py)
         # sdwui token_merging_ratio / _img2img / _hr options (0 = off)
         self.token_merging = {k: 0.0 for k in _TOME_OPTIONS}
+        # sdwui hypertile_* options
+        self.hypertile = {k: d for k, (_, _, d) in _HYPERTILE_OPTIONS.items()}
 
 
 def _b64_png(img: torch.Tensor) -> str:
@@ -651,6 +690,19 @@ def create_app(engine: Optional[LocalEngine] = None,
             out[key] = _tome_ratio(value)
         return out
 
+    def _hypertile(req) -> Dict[str, object]:
+        """The Hypertile fields of a request: override_settings beats the
+        global option; every value sent is validated, used or not."""
+        ov = req.override_settings or {}
+        out = {}
+        for key, (field, _, _) in _HYPERTILE_OPTIONS.items():
+            value = state.hypertile[key]
+            if key in ov:
+                value = _hypertile_value(key, ov[key])
+            if field is not None:
+                out[field] = value
+        return out
+
     def _overrides(req: Txt2ImgRequest):
         """Per-request override_settings (sdwui convention)."""
         ov = req.override_settings or {}
@@ -713,6 +765,7 @@ def create_app(engine: Optional[LocalEngine] = None,
             eta_noise_seed_delta=ensd,
             randn_source=randn_source,
             **_tome_ratios(req),
+            **_hypertile(req),
             tiling=req.tiling,
             s_churn=req.s_churn,
             s_tmin=req.s_tmin,
@@ -788,6 +841,7 @@ def create_app(engine: Optional[LocalEngine] = None,
             eta_noise_seed_delta=ensd,
             randn_source=randn_source,
             **_tome_ratios(req),
+            **_hypertile(req),
             tiling=req.tiling,
             s_churn=req.s_churn,
             s_tmin=req.s_tmin,
@@ -830,6 +884,11 @@ def create_app(engine: Optional[LocalEngine] = None,
         for key in _TOME_OPTIONS:
             if key in extras:
                 state.token_merging[key] = _tome_ratio(extras[key])
+        hypertile = {
+            key: _hypertile_value(key, extras[key])
+            for key in _HYPERTILE_OPTIONS if key in extras
+        }
+        state.hypertile.update(hypertile)
         if req.sd_model_checkpoint and req.sd_model_checkpoint != state.current_model:
             name = req.sd_model_checkpoint
             if name not in available_models():
@@ -861,6 +920,7 @@ def create_app(engine: Optional[LocalEngine] = None,
             "eta_noise_seed_delta": state.ensd,
             "randn_source": state.randn_source,
             **state.token_merging,
+            **state.hypertile,
         }
 
     @app.get("/sdapi/v1/sd-models")

@@ -35,6 +35,7 @@ PAGE = """<!DOCTYPE html>
  token merging <input id="tome" type="range" min="0" max="0.9" step="0.1"
    value="0" oninput="document.getElementById('tome_v').textContent=this.value"/>
  <span id="tome_v">0</span>
+ <label><input id="hypertile" type="checkbox"/> Hypertile</label>
  <button>generate</button>
  <button type="button" onclick="fetch('/sdapi/v1/interrupt',{method:'POST'})">
    interrupt</button>
@@ -159,6 +160,9 @@ async function gen(ev){
   };
   const tome = parseFloat(document.getElementById('tome').value);
   if(tome > 0) body.override_settings = {token_merging_ratio: tome};
+  if(document.getElementById('hypertile').checked)
+    body.override_settings = Object.assign(body.override_settings || {},
+                                           {hypertile_enable_unet: true});
   const r = await fetch('/sdapi/v1/txt2img', {method:'POST',
     headers:{'Content-Type':'application/json'}, body: JSON.stringify(body)});
   const out = await r.json();

@@ -15,7 +15,7 @@ hand-written implicit-GEMM kernels in a later pass).
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -179,6 +179,12 @@ class CrossAttention(nn.Module):
     # per-region loop (A/B timing, comparison tests). CPU, non-bf16 tensors
     # and head dims without a flash kernel take the loop either way.
     fused_regional = True
+    # Hypertile windows on the GPU: True runs the flash kernel's windowed
+    # addressing mode on the strided q/k/v views (no copies); False
+    # materialises the windows and calls the plain kernel (A/B timing,
+    # comparison tests). CPU, non-bf16 tensors and head dims without a
+    # flash kernel take the copies either way.
+    window_native = True
 
     def __init__(self, query_dim: int, context_dim: int, heads: int):
         super().__init__()
@@ -256,8 +262,14 @@ class CrossAttention(nn.Module):
         return ops.attention_blend_bshd(q, k, v, w, tabs[0], tabs[1])
 
     def forward(
-        self, x: torch.Tensor, context: Optional[torch.Tensor] = None
+        self,
+        x: torch.Tensor,
+        context: Optional[torch.Tensor] = None,
+        window: Optional[Tuple[int, int, int, int]] = None,
     ) -> torch.Tensor:
+        """window = (gh, gw, th, tw): self-attention (context None) runs
+        inside the th x tw windows of the gh x gw token grid (Hypertile);
+        ignored with a context."""
         import torch.nn.functional as F
 
         b, s, d = x.shape
@@ -270,6 +282,14 @@ class CrossAttention(nn.Module):
             q = qkv[..., :d].unflatten(-1, hd)
             k = qkv[..., d:2 * d].unflatten(-1, hd)
             v = qkv[..., 2 * d:].unflatten(-1, hd)
+            if window is not None:
+                # the QKV GEMM and to_out act per token, so only the
+                # attention itself has to know about the windows
+                out = ops.attention_window_bshd(
+                    q, k, v, grid=window[:2], window=window[2:],
+                    native=self.window_native,
+                )
+                return self.to_out(out.reshape(b, s, d))
         elif torch.is_tensor(context):
             q = self.to_q(x).unflatten(-1, hd)
             kv = F.linear(context, self._wcat(("to_k", "to_v")))
@@ -365,14 +385,19 @@ class BasicTransformerBlock(nn.Module):
             node_max, node_idx = ops.tome_match(x.float(), h, w)
         return ops.tome_plan(node_max, node_idx, h, w, r)
 
-    def forward(self, x, context, hw=None):
+    def forward(self, x, context, hw=None, window=None):
+        """window = (gh, gw, th, tw): Hypertile windows of the self-
+        attention. A block that merges tokens (r > 0) keeps token merging
+        and ignores its window."""
         from .layers import _fp32_cached
 
         plan = None
         if self.tome_ratio > 0.0 and hw is not None:
             plan = self._tome_plan(x, hw)
         gather = None
-        if plan is None:
+        if plan is None and window is not None:
+            h = self.attn1(self.norm1(x), window=window)
+        elif plan is None:
             h = self.attn1(self.norm1(x))
         elif self.tome_native or not x.is_cuda:
             h = self.attn1(ops.tome_merge(self.norm1(x), plan))
@@ -405,15 +430,33 @@ class SpatialTransformer(nn.Module):
             for _ in range(depth)
         )
         self.proj_out = nn.Linear(channels, channels)
+        # Hypertile: the stage's depth (rank of its resolution among the
+        # UNet's transformer stages, finest 0; UNetModel assigns it) and,
+        # per pass, (width, height, max_tile) or None (UNetModel.set_hypertile)
+        self.hypertile_depth = 0
+        self.hypertile = None
+
+    def _window(self, h: int, w: int):
+        """(gh, gw, th, tw) of this stage's self-attentions, or None."""
+        if self.hypertile is None:
+            return None
+        width, height, max_tile = self.hypertile
+        nh, nw = ops.hypertile_windows(
+            width, height, h, w, self.hypertile_depth, max_tile
+        )
+        if nh * nw == 1:
+            return None
+        return (h, w, h // nh, w // nw)
 
     def forward(self, x: torch.Tensor, context: torch.Tensor) -> torch.Tensor:
         b, c, h, w = x.shape
+        window = self._window(h, w)
         residual = x
         x = self.norm(x)
         x = x.permute(0, 2, 3, 1).reshape(b, h * w, c)
         x = self.proj_in(x)
         for blk in self.blocks:
-            x = blk(x, context, (h, w))
+            x = blk(x, context, (h, w), window)
         x = self.proj_out(x)
         x = x.reshape(b, h, w, c).permute(0, 3, 1, 2)
         # the add also emits the next ResBlock's GroupNorm partials
@@ -481,6 +524,9 @@ class UNetModel(nn.Module):
         # applies there only); a plain list, the modules are registered below
         level0: List[nn.Module] = []
         self._level0 = level0
+        # every (level, SpatialTransformer) of the down and up paths
+        stage_levels: List[Tuple[int, nn.Module]] = []
+        self._stage_levels = stage_levels
         skip_chs = [ch]
         cur = ch
         levels = len(cfg.channel_mult)
@@ -501,6 +547,7 @@ class UNetModel(nn.Module):
                     )
                     if lvl == 0:
                         level0.append(mods[-1])
+                    stage_levels.append((lvl, mods[-1]))
                 self.down.append(_Seq(*mods))
                 skip_chs.append(cur)
             if lvl != levels - 1:
@@ -533,12 +580,21 @@ class UNetModel(nn.Module):
                     )
                     if lvl == 0:
                         level0.append(mods[-1])
+                    stage_levels.append((lvl, mods[-1]))
                 if lvl != 0 and i == cfg.num_res_blocks:
                     mods.append(Upsample(cur))
                 self.up.append(_Seq(*mods))
 
         self.norm_out = FusedGroupNorm(cur, cfg.groups, silu=True)
         self.conv_out = SDConv2d(cur, cfg.out_channels, 3, padding=1)
+
+        # Hypertile depths: the rank of a stage's level among the levels
+        # that have transformers, finest first; the middle block counts one
+        # deeper than the coarsest of them
+        tlevels = [lvl for lvl in range(levels) if cfg.transformer_depth[lvl] > 0]
+        for lvl, stage in self._stage_levels:
+            stage.hypertile_depth = tlevels.index(lvl)
+        self.mid.mods[1].hypertile_depth = len(tlevels)
 
     def level0_blocks(self) -> List["BasicTransformerBlock"]:
         """The transformer blocks that see the full latent grid (level 0,
@@ -549,6 +605,38 @@ class UNetModel(nn.Module):
         """Token merging ratio of the level-0 self-attentions (0 = off)."""
         for blk in self.level0_blocks():
             blk.tome_ratio = float(ratio)
+
+    def spatial_transformers(self) -> List["SpatialTransformer"]:
+        """Every SpatialTransformer: down path, middle block, up path."""
+        return [st for _, st in self._stage_levels] + [self.mid.mods[1]]
+
+    def set_hypertile(
+        self,
+        enabled: bool,
+        width: int = 0,
+        height: int = 0,
+        max_depth: int = 3,
+        max_tile: int = 256,
+    ) -> None:
+        """Hypertile for one pass of width x height pixels: every stage up
+        to max_depth computes its windows from its actual feature-map size
+        (ops.hypertile_windows); deeper stages, and all of them when not
+        enabled, run as without it."""
+        for st in self.spatial_transformers():
+            on = enabled and st.hypertile_depth <= max_depth
+            st.hypertile = (int(width), int(height), int(max_tile)) if on else None
+
+    def hypertile_plan(self, lat_h: int, lat_w: int) -> tuple:
+        """The (gh, gw, th, tw) or None of every SpatialTransformer, in
+        spatial_transformers() order, for a lat_h x lat_w latent under the
+        current set_hypertile state (each Downsample halves, rounding up)."""
+        sizes = [(lat_h, lat_w)]
+        for _ in range(len(self.cfg.channel_mult) - 1):
+            h, w = sizes[-1]
+            sizes.append(((h + 1) // 2, (w + 1) // 2))
+        plan = [st._window(*sizes[lvl]) for lvl, st in self._stage_levels]
+        plan.append(self.mid.mods[1]._window(*sizes[-1]))
+        return tuple(plan)
 
     def forward(
         self,

@@ -482,6 +482,164 @@ def attention_bshd(
 
 
 # ---------------------------------------------------------------------------
+# Hypertile: self-attention inside rectangular windows of the token grid
+# ---------------------------------------------------------------------------
+def _window_extent(n: int, least: int) -> int:
+    """The smallest divisor of n that is >= least (n itself at the latest)."""
+    for t in range(max(1, least), n + 1):
+        if n % t == 0:
+            return t
+    return n
+
+
+def hypertile_windows(
+    width: int, height: int, h: int, w: int, depth: int, max_tile: int = 256
+) -> Tuple[int, int]:
+    """(nh, nw): how many windows a self-attention layer's h x w token grid
+    is cut into, for a pass of width x height pixels. depth is the rank of
+    the layer's resolution among the UNet's transformer stages (finest 0).
+
+    The host's rule at swap size 1, deterministic: P = the largest power of
+    two dividing gcd(width, height); T = min(max_tile, P); L = max(128, T)
+    // 8; along each axis the window is the smallest divisor of the extent
+    that is >= min(L * 2**depth, extent). (1, 1) means the layer is left
+    alone; the max_depth cut-off is the caller's (UNetModel.set_hypertile).
+    """
+    for name, val in (("width", width), ("height", height), ("h", h), ("w", w)):
+        if isinstance(val, bool) or not isinstance(val, int) or val < 1:
+            raise ValueError(f"hypertile_windows: {name} must be a positive "
+                             f"integer (got {val!r})")
+    if isinstance(depth, bool) or not isinstance(depth, int) or depth < 0:
+        raise ValueError(f"hypertile_windows: depth must be an integer >= 0 "
+                         f"(got {depth!r})")
+    if (isinstance(max_tile, bool) or not isinstance(max_tile, int)
+            or max_tile < 0):
+        raise ValueError(f"hypertile_windows: max_tile must be an integer "
+                         f">= 0 (got {max_tile!r})")
+    g = math.gcd(width, height)
+    p = g & -g
+    least = max(128, min(max_tile, p)) // 8 * 2 ** depth
+    th = _window_extent(h, min(least, h))
+    tw = _window_extent(w, min(least, w))
+    return h // th, w // tw
+
+
+def _window_args(name, q, k, v, grid, window):
+    """Validated (B, S, H, D, gh, gw, th, tw) of a windowed attention call."""
+    for n, t in (("q", q), ("k", k), ("v", v)):
+        if not torch.is_tensor(t) or t.dim() != 4:
+            raise ValueError(f"{name}: {n} must be a [B, S, H, D] tensor")
+    if tuple(k.shape) != tuple(q.shape) or tuple(v.shape) != tuple(q.shape):
+        raise ValueError(f"{name}: q, k and v must have one shape (self-"
+                         f"attention); got {tuple(q.shape)}, "
+                         f"{tuple(k.shape)}, {tuple(v.shape)}")
+    if k.device != q.device or v.device != q.device:
+        raise ValueError(f"{name}: q, k and v must share a device")
+    pairs = []
+    for n, pair in (("grid", grid), ("window", window)):
+        try:
+            a, b = pair
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}: {n} must be a pair of integers "
+                             f"(got {pair!r})") from None
+        for x in (a, b):
+            if isinstance(x, bool) or not isinstance(x, int) or x < 1:
+                raise ValueError(f"{name}: {n} must hold positive integers "
+                                 f"(got {pair!r})")
+        pairs.append((a, b))
+    (gh, gw), (th, tw) = pairs
+    B, S, H, D = q.shape
+    if B < 1 or H < 1 or D < 1:
+        raise ValueError(f"{name}: q, k and v must be non-empty")
+    if gh * gw != S:
+        raise ValueError(f"{name}: grid {gh}x{gw} does not match the token "
+                         f"count {S}")
+    if gh % th or gw % tw:
+        raise ValueError(f"{name}: window {th}x{tw} does not divide the "
+                         f"grid {gh}x{gw}")
+    return B, S, H, D, gh, gw, th, tw
+
+
+def window_split(x: torch.Tensor, grid, window) -> torch.Tensor:
+    """[B, gh*gw, ...] -> [B*nh*nw, th*tw, ...]: the windows of the token
+    grid as batch rows (a copy), window (i, j) of batch b at row
+    (b*nh + i)*nw + j. The host's `b (nh h nw w) c -> (b nh nw) (h w) c`."""
+    (gh, gw), (th, tw) = grid, window
+    nh, nw = gh // th, gw // tw
+    b, rest = x.shape[0], tuple(x.shape[2:])
+    nd = len(rest)
+    x = x.reshape(b, nh, th, nw, tw, *rest)
+    x = x.permute(0, 1, 3, 2, 4, *range(5, 5 + nd))
+    return x.reshape(b * nh * nw, th * tw, *rest)
+
+
+def window_merge(x: torch.Tensor, grid, window) -> torch.Tensor:
+    """The inverse of window_split: [B*nh*nw, th*tw, ...] -> [B, gh*gw, ...]."""
+    (gh, gw), (th, tw) = grid, window
+    nh, nw = gh // th, gw // tw
+    b, rest = x.shape[0] // (nh * nw), tuple(x.shape[2:])
+    nd = len(rest)
+    x = x.reshape(b, nh, nw, th, tw, *rest)
+    x = x.permute(0, 1, 3, 2, 4, *range(5, 5 + nd))
+    return x.reshape(b, gh * gw, *rest)
+
+
+def attention_window_supported(q, k, v) -> bool:
+    """True when attention_window_bshd runs the windowed kernel on these
+    tensors: on the GPU, bf16, a head dim with a flash kernel, unit stride
+    in D and 16-byte-aligned rows (what the fused QKV slices have)."""
+    if not (q.is_cuda and k.is_cuda and v.is_cuda
+            and q.dtype == k.dtype == v.dtype == torch.bfloat16
+            and ext().flash_supported(q.shape[-1])):
+        return False
+    for t in (q, k, v):
+        if t.stride(-1) != 1 or t.data_ptr() % 16:
+            return False
+        if any(t.shape[i] != 1 and t.stride(i) % 8 for i in range(3)):
+            return False
+    return True
+
+
+def attention_window_bshd(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    grid,
+    window,
+    scale: Optional[float] = None,
+    native: bool = True,
+) -> torch.Tensor:
+    """Self-attention inside the windows of a token grid (Hypertile).
+
+    q, k, v: [B, gh*gw, H, D] (strided views as attention_bshd takes), grid
+    = (gh, gw), window = (th, tw) with th | gh and tw | gw. Token (Y, X)
+    attends to the th*tw tokens of window (Y // th, X // tw); the output is
+    [B, gh*gw, H, D] in the original token order.
+
+    GPU, bf16, flash head dim: flash_fwd_bf16_v3's WIN mode reads q/k/v and
+    writes the output in place, no rearranged copies. native=False (A/B
+    timing, comparison tests) and every other GPU case (D=512, fp32): the
+    windows are materialised (window_split) and go through attention_bshd.
+    CPU: the same rearrangement on the fp32 reference (the oracle).
+    window == grid returns exactly what attention_bshd returns.
+    """
+    name = "attention_window"
+    B, S, H, D, gh, gw, th, tw = _window_args(name, q, k, v, grid, window)
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    if (th, tw) == (gh, gw):
+        return attention_bshd(q, k, v, scale)
+    if q.is_cuda and native and attention_window_supported(q, k, v):
+        return ext().attention_window_bshd(q, k, v, gh, gw, th, tw, scale)
+    g, w = (gh, gw), (th, tw)
+    out = attention_bshd(
+        window_split(q, g, w), window_split(k, g, w), window_split(v, g, w),
+        scale,
+    )
+    return window_merge(out, g, w)
+
+
+# ---------------------------------------------------------------------------
 # multi-context attention blend (regional prompting, decoupled cross-attn)
 # ---------------------------------------------------------------------------
 def attention_blend_supported(q, k, v) -> bool:

@@ -31,7 +31,8 @@
 //    count as the key bound.
 //  * flash_fwd_bf16_v3: the same geometry with double-buffered row-major
 //    tiles, hardware-transpose V reads, async staging and defer-max; it
-//    shares the helpers, not the tile step.
+//    shares the helpers, not the tile step. Its WIN flag is the windowed
+//    addressing mode (attention inside the windows of a token grid).
 //
 // These kernels sit at the 256-VGPR edge, and how far a piece is shared is
 // set by what keeps their register allocation (table and method in
@@ -63,6 +64,25 @@ struct AttnStrides {
   long kb, kh, kr;
   long vb, vh, vr;
   long ob, oh, or_;
+};
+
+// Windowed self-attention (v3's WIN mode): the S = gh*gw tokens of a batch
+// row are a gh x gw grid cut into nh x nw windows of th x tw tokens, and
+// attention runs inside each window. In-window row r of window (i, j) is
+// grid token ((i*th + r/tw) * gw + j*tw + r%tw), addressed with the row
+// strides of AttnStrides: no rearranged copies of q, k, v or the output.
+struct AttnWindow {
+  int nh, nw;  // windows per grid column / row
+  int th, tw;  // window size (tokens)
+  int gw;      // grid width: tokens per grid row
+};
+// v3's strides argument: AttnStrides alone, plus the window when WIN. The
+// WIN = false kernels keep the argument block (and the code) they had.
+template <bool WIN>
+struct AttnArgs : AttnStrides {};
+template <>
+struct AttnArgs<true> : AttnStrides {
+  AttnWindow win;
 };
 
 // tile geometry of every kernel here, as functions of the padded head dim
@@ -346,11 +366,23 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_kernel(
 //    which fp32 accumulation absorbs (THR=8 -> P<=256).
 //  * s_setprio(1) brackets around the MFMA clusters (T5).
 // ---------------------------------------------------------------------------
-template <int DPAD, int QS = v3_qs(DPAD)>
+//
+// WIN is the windowed addressing mode, a compile-time flag like the conv
+// kernels' WRAP and add+LN's GATHER: blockIdx.y walks (batch, window, head),
+// the launch passes Sq = Sk = th*tw, and every row index is an
+// in-window row mapped to its grid token (AttnWindow). The tile loop stays
+// division-free: each staged piece carries its x within the window row next
+// to its pointer and advances by (64 / tw, 64 % tw) with one conditional
+// carry; when tw divides 64 the carry never fires and the advance is the
+// uniform delta again. Only the Q load, the clamped re-derivation on the
+// ragged last tile and the epilogue divide (once per row). The arithmetic
+// and the tile order are v3's, so a windowed call is bit-equal to v3 on
+// materialised window copies.
+template <int DPAD, int QS = v3_qs(DPAD), bool WIN = false>
 __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
     const __hip_bfloat16 *__restrict__ Q, const __hip_bfloat16 *__restrict__ K,
     const __hip_bfloat16 *__restrict__ V, __hip_bfloat16 *__restrict__ O,
-    int H, long Sq, long Sk, int D, float scale, AttnStrides st) {
+    int H, long Sq, long Sk, int D, float scale, AttnArgs<WIN> st) {
   using G = AttnGeom<DPAD>;
   constexpr int KVB = G::KVB, PADK = G::PADK, NC = G::NC, DV = G::DV,
                 ND = G::ND;
@@ -380,19 +412,45 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
   __shared__ __align__(16) __bf16 kt[2][KVB][DPAD + PADK];
   __shared__ __align__(16) __bf16 vt2[2][KVB][RSV];
 
+  // WIN: blockIdx.y is (batch, window, head), head fastest
   const int bh = blockIdx.y;
   const int qblk = blockIdx.x;
-  const int bb = bh / H, hh = bh % H;
+  int bb = bh / H;
+  const int hh = bh % H;
   const int wid = threadIdx.x / WAVE;
   const int lane = threadIdx.x % WAVE;
   const int lq = lane % 32;
   const int half = lane / 32;
   const long q0 = (long)qblk * (QS * 128) + wid * (QS * 32);
 
+  long w0 = 0;  // WIN: the window's first grid token
+  if constexpr (WIN) {
+    const int nwin = st.win.nh * st.win.nw;
+    const int wi = bb % nwin;
+    bb /= nwin;
+    w0 = (long)(wi / st.win.nw) * st.win.th * st.win.gw +
+         (long)(wi % st.win.nw) * st.win.tw;
+  }
   const __hip_bfloat16 *Qb = Q + bb * st.qb + hh * st.qh;
   const __hip_bfloat16 *Kb = K + bb * st.kb + hh * st.kh;
   const __hip_bfloat16 *Vb = V + bb * st.vb + hh * st.vh;
   __hip_bfloat16 *Ob = O + bb * st.ob + hh * st.oh;
+  if constexpr (WIN) {
+    Qb += w0 * st.qr;
+    Kb += w0 * st.kr;
+    Vb += w0 * st.vr;
+    Ob += w0 * st.or_;
+  }
+  // in-window row (already clamped below th*tw) -> grid token offset from
+  // the window's first token; the identity without windows
+  const auto grid_row = [&](long r) -> long {
+    if constexpr (WIN) {
+      const int y = (int)r / st.win.tw;
+      return (long)y * st.win.gw + ((int)r - y * st.win.tw);
+    } else {
+      return r;
+    }
+  };
 
   // staged-piece coordinates: pieces [0,NG) are K rows, [NG,2NG) V rows;
   // NG is a multiple of 64 so the K/V split is wave-uniform and every
@@ -418,9 +476,17 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
   const float l2scale = scale * 1.4426950408889634f;
   bf16x8 qf[QS][NC];
 #pragma unroll
-  for (int qs = 0; qs < QS; ++qs)
-    load_q_frags<true>(qf[qs], Qb, st.qr, q0 + qs * 32 + lq, Sq, D, half,
-                       l2scale);
+  for (int qs = 0; qs < QS; ++qs) {
+    if constexpr (WIN) {
+      // clamp in the window, then map: the helper's own clamp is a no-op
+      const long qq = q0 + qs * 32 + lq;
+      const long g = grid_row((qq < Sq) ? qq : (Sq - 1));
+      load_q_frags<true>(qf[qs], Qb, st.qr, g, g + 1, D, half, l2scale);
+    } else {
+      load_q_frags<true>(qf[qs], Qb, st.qr, q0 + qs * 32 + lq, Sq, D, half,
+                         l2scale);
+    }
+  }
 
   // per-lane tr-read base LDS byte address (probe-decoded mapping): the
   // per-read row/col deltas are added as small unsigned offsets
@@ -442,14 +508,27 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
   // per-thread running piece pointers: tile 0 clamped; full-tile advances
   // are one uniform-delta 64-bit add instead of strided re-derivation
   const __hip_bfloat16 *pp[NST];
+  int px[WIN ? NST : 1];  // WIN: the piece's x within its window row
 #pragma unroll
   for (int s = 0; s < NST; ++s) {
     int sr, sc; bool v; piece(s, sr, sc, v);
     const long r = (sr < Sk) ? sr : (Sk - 1);
     const int cg = (sc <= dmax) ? sc : dmax;
-    pp[s] = (v ? Vb + r * st.vr : Kb + r * st.kr) + cg * 8;
+    const long g = grid_row(r);
+    pp[s] = (v ? Vb + g * st.vr : Kb + g * st.kr) + cg * 8;
+    if constexpr (WIN) px[s] = (int)r % st.win.tw;
   }
-  const long kdelta = KVB * st.kr, vdelta = KVB * st.vr;
+  // 64 rows on: (64 / tw) grid rows down and 64 % tw to the right, one more
+  // grid row down and tw back when x passes the window's right edge
+  int dx = 0;
+  long rstep = KVB, rcarry = 0;
+  if constexpr (WIN) {
+    dx = KVB % st.win.tw;
+    rstep = (long)(KVB / st.win.tw) * st.win.gw + dx;
+    rcarry = st.win.gw - st.win.tw;
+  }
+  const long kdelta = rstep * st.kr, vdelta = rstep * st.vr;
+  const long kcarry = rcarry * st.kr, vcarry = rcarry * st.vr;
 
   // prologue: issue tile 0's loads (clamped; OOB keys masked at score time)
   bf16x8 stg[ASYNC ? NST : 1];
@@ -480,14 +559,24 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
     // the clamped re-derivation when it is the ragged last one
     if (kv + 2 * KVB <= Sk) {
 #pragma unroll
-      for (int s = 0; s < NST; ++s)
-        pp[s] += (threadIdx.x + s * 256 >= NG) ? vdelta : kdelta;
+      for (int s = 0; s < NST; ++s) {
+        const bool v = threadIdx.x + s * 256 >= NG;
+        pp[s] += v ? vdelta : kdelta;
+        if constexpr (WIN) {
+          px[s] += dx;
+          if (px[s] >= st.win.tw) {
+            px[s] -= st.win.tw;
+            pp[s] += v ? vcarry : kcarry;
+          }
+        }
+      }
     } else if (kv + KVB < Sk) {
+      // (the next tile is the last: px is not read again)
 #pragma unroll
       for (int s = 0; s < NST; ++s) {
         int sr, sc; bool v; piece(s, sr, sc, v);
         const long rr = kv + KVB + sr;
-        const long r = (rr < Sk) ? rr : (Sk - 1);
+        const long r = grid_row((rr < Sk) ? rr : (Sk - 1));
         const int cg = (sc <= dmax) ? sc : dmax;
         pp[s] = (v ? Vb + r * st.vr : Kb + r * st.kr) + cg * 8;
       }
@@ -622,11 +711,21 @@ __launch_bounds__(256, 2) __global__ void flash_fwd_bf16_v3(
 #pragma unroll
   for (int qs = 0; qs < QS; ++qs) {
     const float linv = 1.0f / fmaxf(l[qs], 1e-30f);
+    // WIN: lane lq maps its own (clamped) row once; the grid token reaches
+    // register r the way 1/l does
+    int gmine = 0;
+    if constexpr (WIN) {
+      const long qm = q0 + qs * 32 + lq;
+      gmine = (int)grid_row((qm < Sq) ? qm : (Sq - 1));
+    }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const float inv = __shfl(linv, crow(r, half), WAVE);
-      const long qq = q0 + qs * 32 + crow(r, half);
+      long qq = q0 + qs * 32 + crow(r, half);
+      int g = 0;
+      if constexpr (WIN) g = __shfl(gmine, crow(r, half), WAVE);
       if (qq >= Sq) continue;
+      if constexpr (WIN) qq = g;
 #pragma unroll
       for (int d = 0; d < ND; ++d)
         if (d * 32 + lq < D)
@@ -840,13 +939,61 @@ static torch::Tensor flash_attention_raw(torch::Tensor q, torch::Tensor k,
     constexpr int DP = decltype(dp)::value;
     TORCH_CHECK(rows == 128 * (run_v2 ? v2_qs(DP) : v3_qs(DP)),
                 "flash: plan rows do not match the instantiation");
-    hipLaunchKernelGGL(
-        run_v2 ? flash_fwd_bf16_kernel<DP> : flash_fwd_bf16_v3<DP>, grid,
-        block, 0, stream, (const __hip_bfloat16 *)q.data_ptr(),
-        (const __hip_bfloat16 *)k.data_ptr(),
-        (const __hip_bfloat16 *)v.data_ptr(),
-        (__hip_bfloat16 *)out.data_ptr(), (int)H, Sq, Sk, (int)D,
-        (float)scale, st);
+    const auto launch = [&](auto kernel, auto args) {
+      hipLaunchKernelGGL(kernel, grid, block, 0, stream,
+                         (const __hip_bfloat16 *)q.data_ptr(),
+                         (const __hip_bfloat16 *)k.data_ptr(),
+                         (const __hip_bfloat16 *)v.data_ptr(),
+                         (__hip_bfloat16 *)out.data_ptr(), (int)H, Sq, Sk,
+                         (int)D, (float)scale, args);
+    };
+    if (run_v2) launch(flash_fwd_bf16_kernel<DP>, st);
+    else launch(flash_fwd_bf16_v3<DP>, AttnArgs<false>{st});
+  });
+  return out;
+}
+
+// The windowed kernel's geometry: {padded head dim, q rows per workgroup}.
+// Windowed calls always run v3 (WIN = true), whatever the window's token
+// count; a head dim without a flash kernel is an error. The launcher below
+// follows this and nothing else decides.
+std::tuple<long, long> attention_window_plan(long d_head) {
+  TORCH_CHECK(flash_supported(d_head), "attention_window: head dim ", d_head,
+              " has no flash kernel");
+  const long dpad = round16(d_head);
+  return {dpad, 128 * v3_qs((int)dpad)};
+}
+
+// q/k/v [B, gh*gw, H, D] (unit stride in D, 16-byte-aligned rows; the caller
+// checked shapes, alignment and that th | gh, tw | gw): attention inside each
+// th x tw window of the gh x gw token grid, output in the original order.
+static torch::Tensor flash_window_raw(torch::Tensor q, torch::Tensor k,
+                                      torch::Tensor v, double scale, long gh,
+                                      long gw, long th, long tw) {
+  const long B = q.size(0), S = q.size(1), H = q.size(2), D = q.size(3);
+  auto out = torch::empty({B, S, H, D}, q.options());
+  AttnArgs<true> args{attn_strides(q, k, v, out, /*bshd=*/true),
+                      AttnWindow{(int)(gh / th), (int)(gw / tw), (int)th,
+                                 (int)tw, (int)gw}};
+  const auto [dpad, qrows] = attention_window_plan(D);
+  const long rows = qrows;  // (a structured binding cannot be captured)
+  const long wtok = th * tw, nblk_y = B * (gh / th) * (gw / tw) * H;
+  TORCH_CHECK(nblk_y <= 65535, "attention_window: batch * windows * heads = ",
+              nblk_y, " exceeds the grid's y extent (65535)");
+  const dim3 grid((unsigned)((wtok + rows - 1) / rows), (unsigned)nblk_y);
+  const dim3 block(256);
+  auto stream = cur_stream();
+
+  dispatch_dpad(dpad, "flash_window", [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    TORCH_CHECK(rows == 128 * v3_qs(DP),
+                "flash_window: plan rows do not match the instantiation");
+    hipLaunchKernelGGL((flash_fwd_bf16_v3<DP, v3_qs(DP), true>), grid, block,
+                       0, stream, (const __hip_bfloat16 *)q.data_ptr(),
+                       (const __hip_bfloat16 *)k.data_ptr(),
+                       (const __hip_bfloat16 *)v.data_ptr(),
+                       (__hip_bfloat16 *)out.data_ptr(), (int)H, wtok, wtok,
+                       (int)D, (float)scale, args);
   });
   return out;
 }

@@ -608,6 +608,46 @@ torch::Tensor attention_fwd_bshd(torch::Tensor q, torch::Tensor k,
   return flash_attention_raw(q, k, v, scale, /*bshd=*/true, force);
 }
 
+torch::Tensor attention_window_bshd(torch::Tensor q, torch::Tensor k,
+                                    torch::Tensor v, long gh, long gw, long th,
+                                    long tw, double scale) {
+  // softmax attention inside each th x tw window of the gh x gw token grid;
+  // everything an address is formed from is checked here, so a bad argument
+  // raises and never becomes an out-of-range read
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4,
+              "attention_window: q/k/v must be [B,S,H,D]");
+  TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda(),
+              "attention_window: q/k/v must be on the GPU");
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16 &&
+                  k.scalar_type() == torch::kBFloat16 &&
+                  v.scalar_type() == torch::kBFloat16 &&
+                  flash_supported(q.size(3)),
+              "attention_window: bf16 q/k/v with a supported head dim only");
+  TORCH_CHECK(q.sizes() == k.sizes() && q.sizes() == v.sizes(),
+              "attention_window: q, k and v shapes differ");
+  TORCH_CHECK(q.size(0) > 0 && q.size(2) > 0,
+              "attention_window: empty q/k/v");
+  TORCH_CHECK(gh > 0 && gw > 0 && gh <= (1L << 30) / gw,
+              "attention_window: grid must be positive and below 2^30 tokens");
+  TORCH_CHECK(q.size(1) == gh * gw, "attention_window: grid ", gh, "x", gw,
+              " does not match the token count ", q.size(1));
+  TORCH_CHECK(th > 0 && th <= gh && gh % th == 0,
+              "attention_window: window height ", th,
+              " must divide the grid height ", gh);
+  TORCH_CHECK(tw > 0 && tw <= gw && gw % tw == 0,
+              "attention_window: window width ", tw,
+              " must divide the grid width ", gw);
+  for (const auto &t : {q, k, v}) {
+    bool rows16 = t.stride(3) == 1 && ((uintptr_t)t.data_ptr()) % 16 == 0;
+    for (int i = 0; i < 3; ++i)
+      rows16 = rows16 && (t.size(i) == 1 || t.stride(i) % 8 == 0);
+    TORCH_CHECK(rows16,
+                "attention_window: q/k/v need unit stride in D and "
+                "16-byte-aligned rows");
+  }
+  return flash_window_raw(q, k, v, scale, gh, gw, th, tw);
+}
+
 torch::Tensor attention_blend_bshd(torch::Tensor q, torch::Tensor k,
                                    torch::Tensor v, torch::Tensor w,
                                    torch::Tensor kv_index,
@@ -801,6 +841,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("k"), py::arg("v"), py::arg("w"), py::arg("kv_index"),
         py::arg("kv_len"), py::arg("scale"));
   m.def("attention_blend_plan", &attention_blend_plan);
+  m.def("attention_window_bshd", &attention_window_bshd, py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("gh"), py::arg("gw"),
+        py::arg("th"), py::arg("tw"), py::arg("scale"));
+  m.def("attention_window_plan", &attention_window_plan);
   m.def("probe_mfma32", &probe_mfma32);
   m.def("probe_mfma16", &probe_mfma16);
   m.def("probe_tr16", &probe_tr16);

@@ -78,6 +78,11 @@ class GenerationRequest:
     token_merging_ratio: float = 0.0
     token_merging_ratio_img2img: float = 0.0
     token_merging_ratio_hr: float = 0.0
+    # Hypertile (see PipelineRequest for semantics)
+    hypertile_unet: bool = False
+    hypertile_unet_secondpass: bool = False
+    hypertile_max_depth: int = 3
+    hypertile_max_tile: int = 256
     init_images: Optional[torch.Tensor] = None  # [B,H,W,3] uint8 (img2img)
     denoising_strength: float = 0.75
     mask_image: Optional[torch.Tensor] = None   # [H,W] uint8, 255=repaint
@@ -173,6 +178,14 @@ class GalleryResult:
     interrupted: bool = False
 
 
+def _hypertile_fields(gen) -> tuple:
+    """The Hypertile settings of a generation, as the plan broadcasts them."""
+    return (
+        bool(gen.hypertile_unet), bool(gen.hypertile_unet_secondpass),
+        int(gen.hypertile_max_depth), int(gen.hypertile_max_tile),
+    )
+
+
 def _job_pipeline_request(
     gen: GenerationRequest, job: Job, init_latents=None
 ) -> PipelineRequest:
@@ -203,6 +216,10 @@ def _job_pipeline_request(
         token_merging_ratio=gen.token_merging_ratio,
         token_merging_ratio_img2img=gen.token_merging_ratio_img2img,
         token_merging_ratio_hr=gen.token_merging_ratio_hr,
+        hypertile_unet=gen.hypertile_unet,
+        hypertile_unet_secondpass=gen.hypertile_unet_secondpass,
+        hypertile_max_depth=gen.hypertile_max_depth,
+        hypertile_max_tile=gen.hypertile_max_tile,
         init_latents=init_latents,
         denoising_strength=gen.denoising_strength,
         mask_image=gen.mask_image,
@@ -1030,10 +1047,13 @@ class DistributedEngine(_EngineBase):
                     gen.token_merging_ratio_img2img,
                     gen.token_merging_ratio_hr,
                 ),
+                _hypertile_fields(gen),
             )
         else:
             plan = None
-        model_name, jobs, randn_source, tome = pg.broadcast_object(plan)
+        model_name, jobs, randn_source, tome, hypertile = (
+            pg.broadcast_object(plan)
+        )
         if randn_source != gen.randn_source:
             # the noise source decides every image: rank 0's choice holds
             gen = replace_dc(gen, randn_source=randn_source)
@@ -1048,6 +1068,15 @@ class DistributedEngine(_EngineBase):
                 token_merging_ratio=tome[0],
                 token_merging_ratio_img2img=tome[1],
                 token_merging_ratio_hr=tome[2],
+            )
+        if hypertile != _hypertile_fields(gen):
+            # and the Hypertile settings: every rank cuts the same windows
+            gen = replace_dc(
+                gen,
+                hypertile_unet=hypertile[0],
+                hypertile_unet_secondpass=hypertile[1],
+                hypertile_max_depth=hypertile[2],
+                hypertile_max_tile=hypertile[3],
             )
         self.set_model(model_name)
         # per-worker checkpoint override (ref ui.py:161-171): purely local —

@@ -127,6 +127,24 @@ def _prompt_sr(gen, value):
     raise RuntimeError("applied specially in run_xyz")  # pragma: no cover
 
 
+def _axis_bool(value) -> bool:
+    """A boolean axis value in the host's spellings (true/false, case-
+    insensitive; also yes/no, on/off, 1/0)."""
+    key = str(value).strip().lower()
+    if key in ("true", "yes", "on", "1"):
+        return True
+    if key in ("false", "no", "off", "0"):
+        return False
+    raise ValueError(f"not a boolean axis value: {value!r}")
+
+
+def _axis_int_in(value, lo: int, hi: int, what: str) -> int:
+    v = int(value)
+    if not lo <= v <= hi:
+        raise ValueError(f"Hypertile {what} {v} is outside {lo}..{hi}")
+    return v
+
+
 # Index-addressable axis list (published via /sdapi/v1/script-info and
 # docs/api_reference.md). The first eight match the host's dropdown order;
 # string names are the version-proof way to address any of them.
@@ -170,6 +188,26 @@ AXIS_OPTIONS: List[AxisOption] = [
         "Token merging ratio", "float",
         lambda g, v: replace(g, token_merging_ratio=float(v)),
     ),
+    AxisOption(
+        "Hypertile U-Net first pass enabled", "str",
+        lambda g, v: replace(g, hypertile_unet=_axis_bool(v)),
+    ),
+    AxisOption(
+        "Hypertile U-Net second pass enabled", "str",
+        lambda g, v: replace(g, hypertile_unet_secondpass=_axis_bool(v)),
+    ),
+    AxisOption(
+        "Hypertile U-Net max depth", "int",
+        lambda g, v: replace(
+            g, hypertile_max_depth=_axis_int_in(v, 0, 3, "max depth")
+        ),
+    ),
+    AxisOption(
+        "Hypertile U-Net max tile size", "int",
+        lambda g, v: replace(
+            g, hypertile_max_tile=_axis_int_in(v, 0, 512, "max tile size")
+        ),
+    ),
 ]
 
 _BY_NAME = {o.name.lower(): i for i, o in enumerate(AXIS_OPTIONS)}
@@ -186,6 +224,12 @@ _BY_NAME.update({
     "eta noise seed delta": 19,
     "rng": 23, "randn_source": 23, "random number generator source": 23,
     "token_merging_ratio": 24, "tome": 24,
+    # the host's own axis labels and the option names
+    "[hypertile] unet first pass enabled": 25, "hypertile_enable_unet": 25,
+    "[hypertile] unet second pass enabled": 26,
+    "hypertile_enable_unet_secondpass": 26,
+    "[hypertile] unet max depth": 27, "hypertile_max_depth_unet": 27,
+    "[hypertile] unet max tile size": 28, "hypertile_max_tile_unet": 28,
 })
 
 

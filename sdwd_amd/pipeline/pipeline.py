@@ -104,6 +104,14 @@ class PipelineRequest:
     token_merging_ratio: float = 0.0
     token_merging_ratio_img2img: float = 0.0
     token_merging_ratio_hr: float = 0.0
+    # Hypertile (sdwui hypertile_enable_unet / _secondpass / max_depth_unet /
+    # max_tile_unet): self-attention inside rectangular windows of the token
+    # grid. The first pass is windowed iff hypertile_unet, the hires pass
+    # iff either switch is set. max_depth 0..3, max_tile 0..512 pixels.
+    hypertile_unet: bool = False
+    hypertile_unet_secondpass: bool = False
+    hypertile_max_depth: int = 3
+    hypertile_max_tile: int = 256
     # k-diffusion stochasticity (sdwui Sampler parameters section)
     s_churn: float = 0.0
     s_tmin: float = 0.0
@@ -255,6 +263,15 @@ def _clamp_tome_ratio(value) -> float:
     return min(0.9, max(0.0, float(value or 0.0)))
 
 
+def hypertile_enabled_for(req, hr: bool = False) -> bool:
+    """Whether a pass of the request runs Hypertile: the first pass iff
+    hypertile_unet, the hires pass iff that or hypertile_unet_secondpass."""
+    on = bool(getattr(req, "hypertile_unet", False))
+    if hr:
+        on = on or bool(getattr(req, "hypertile_unet_secondpass", False))
+    return on
+
+
 def token_merging_ratio_for(req, hr: bool = False) -> float:
     """The token merging ratio in force for one pass of req (sdwui's
     get_token_merging_ratio): the hires pass takes token_merging_ratio_hr,
@@ -371,6 +388,7 @@ class StableDiffusionPipeline:
         self.lora = LoraManager(self.model.unet)
         self._tiling = False
         self._tome_ratio = 0.0
+        self._hypertile_plan = None
         self._last_preview = None  # latest denoise-loop latents (preview)
         self._denoiser = GraphedDenoiser(
             lambda x, ts, ctx, y: self.model.unet(x, ts, ctx, y=y),
@@ -606,6 +624,30 @@ class StableDiffusionPipeline:
             self._wholestep_cache.clear()
             self._tome_ratio = ratio
 
+    def _set_hypertile(self, req, width: int, height: int,
+                       hr: bool = False) -> None:
+        """Hypertile windows of the UNet's self-attentions for one pass of
+        width x height pixels (the ControlNet copies and the VAE are not
+        patched). Captured graphs baked the launches of the old windows, so
+        a change of the effective windows drops them, as a change of the
+        token merging ratio does; the same windows keep them."""
+        unet = self.model.unet
+        # the stages are set every time: pipelines may share one model
+        unet.set_hypertile(
+            hypertile_enabled_for(req, hr), width, height,
+            int(req.hypertile_max_depth), int(req.hypertile_max_tile),
+        )
+        f = self.model.vae.cfg.downsample_factor
+        plan = unet.hypertile_plan(height // f, width // f)
+        if not any(plan):
+            plan = None
+        if plan != self._hypertile_plan:
+            self._denoiser.cache.clear()
+            for graphed in self._wholestep_cache.values():
+                graphed.cache.clear()
+            self._wholestep_cache.clear()
+            self._hypertile_plan = plan
+
     # -- the denoise loop ----------------------------------------------------
     @torch.no_grad()
     def generate(
@@ -640,6 +682,7 @@ class StableDiffusionPipeline:
             self._tiling = req.tiling
         tome_ratio = token_merging_ratio_for(req)
         self._set_tome_ratio(tome_ratio)
+        self._set_hypertile(req, req.width, req.height)
         b = req.batch_size
         f = self.model.vae.cfg.downsample_factor
         lat_h, lat_w = req.height // f, req.width // f
@@ -1257,6 +1300,9 @@ class StableDiffusionPipeline:
                     crop_x // 2 : x.shape[3] - (crop_x - crop_x // 2),
                 ]
             self._set_tome_ratio(token_merging_ratio_for(req, hr=True))
+            self._set_hypertile(
+                req, x.shape[3] * f, x.shape[2] * f, hr=True
+            )
             hr_sampler = req.hr_sampler_name or req.sampler_name
             hsched = schedule_for(hr_sampler, hr_steps, req.scheduler)
             start = max(
@@ -1376,6 +1422,23 @@ class StableDiffusionPipeline:
                 ", Token merging ratio hr: "
                 f"{token_merging_ratio_for(req, hr=True)}"
             )
+        hr_on = hires_active(
+            req.enable_hr, req.hr_scale, req.hr_resize_x, req.hr_resize_y
+        )
+        if req.hypertile_unet:
+            extra += ", Hypertile U-Net: True"
+        if req.hypertile_unet_secondpass and hr_on:
+            extra += ", Hypertile U-Net second pass: True"
+        if req.hypertile_unet or (req.hypertile_unet_secondpass and hr_on):
+            if int(req.hypertile_max_depth) != 3:
+                extra += (
+                    f", Hypertile U-Net max depth: {int(req.hypertile_max_depth)}"
+                )
+            if int(req.hypertile_max_tile) != 256:
+                extra += (
+                    ", Hypertile U-Net max tile size: "
+                    f"{int(req.hypertile_max_tile)}"
+                )
         prompt_of = (
             (lambda i: req.prompts[i]) if per_image else (lambda i: req.prompt)
         )

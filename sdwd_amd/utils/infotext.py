@@ -24,6 +24,10 @@ _REQUEST_FIELDS = {
     "ENSD": "eta_noise_seed_delta",
     "Token merging ratio": "token_merging_ratio",
     "Token merging ratio hr": "token_merging_ratio_hr",
+    "Hypertile U-Net": "hypertile_unet",
+    "Hypertile U-Net second pass": "hypertile_unet_secondpass",
+    "Hypertile U-Net max depth": "hypertile_max_depth",
+    "Hypertile U-Net max tile size": "hypertile_max_tile",
 }
 
 
@@ -43,7 +47,11 @@ def parse_infotext(text: str) -> Dict[str, str]:
     settings an image cannot be reproduced without are also returned under
     their request field names: ``RNG`` as ``randn_source``, ``ENSD`` as
     ``eta_noise_seed_delta``, ``Token merging ratio`` and ``Token merging
-    ratio hr`` as ``token_merging_ratio`` and ``token_merging_ratio_hr``.
+    ratio hr`` as ``token_merging_ratio`` and ``token_merging_ratio_hr``,
+    ``Hypertile U-Net`` / ``... second pass`` / ``... max depth`` / ``... max
+    tile size`` as ``hypertile_unet``, ``hypertile_unet_secondpass``,
+    ``hypertile_max_depth`` and ``hypertile_max_tile`` (values stay strings,
+    as every other entry).
     """
     lines = (text or "").split("\n")
     # the parameter line is the LAST line iff it parses as k:v pairs

@@ -49,6 +49,15 @@ def main() -> int:
                     help="ancestral/SDE noise multiplier (sdwui Eta)")
     ap.add_argument("--vae", default="",
                     help="standalone VAE name from SDWD_VAE_DIR")
+    ap.add_argument("--hypertile", action="store_true",
+                    help="Hypertile on the U-Net (hypertile_enable_unet)")
+    ap.add_argument("--hypertile-secondpass", action="store_true",
+                    help="Hypertile on the hires pass only")
+    ap.add_argument("--hypertile-max-depth", type=int, default=3)
+    ap.add_argument("--hypertile-max-tile", type=int, default=256)
+    ap.add_argument("--repeat", type=int, default=1,
+                    help="generate this many times (same request) and print "
+                         "each run's seconds; the last run is saved")
     ap.add_argument("--out", default="outputs")
     ap.add_argument("--benchmark", action="store_true",
                     help="re-benchmark ranks before generating")
@@ -77,7 +86,7 @@ def main() -> int:
             img = decode_png(fh.read())
         init_images = img[None]
 
-    res = engine.generate(
+    gen = (
         GenerationRequest(
             prompt=args.prompt,
             prompts=prompts,
@@ -101,8 +110,16 @@ def main() -> int:
             hr_upscaler=args.hr_upscaler,
             refiner_model=args.refiner,
             refiner_switch_at=args.refiner_switch_at,
+            hypertile_unet=args.hypertile,
+            hypertile_unet_secondpass=args.hypertile_secondpass,
+            hypertile_max_depth=args.hypertile_max_depth,
+            hypertile_max_tile=args.hypertile_max_tile,
         )
     )
+    for run in range(max(1, args.repeat)):
+        res = engine.generate(gen)
+        if args.repeat > 1:
+            print(f"run {run}: {res.elapsed:.4f}s", flush=True)
     os.makedirs(args.out, exist_ok=True)
     for i in range(res.images.shape[0]):
         path = os.path.join(args.out, f"{res.seeds[i]}_{i:03d}.png")
