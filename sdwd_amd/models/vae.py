@@ -66,7 +66,14 @@ class VAEResBlock(nn.Module):
 
 
 class VAEAttention(nn.Module):
-    """Single-head spatial attention mid-block (seq = H*W, one head)."""
+    """Single-head spatial attention mid-block (seq = H*W, one head).
+
+    flash: route head dims 256 / 512 (every shipped VAE is 512) to the wide
+    flash kernel (ops.attention_wide) instead of the composed GEMM + softmax
+    route of ops.attention. Default set by measurement
+    (profiles/r13_attention_wide.md)."""
+
+    flash = True
 
     def __init__(self, ch: int, groups: int):
         super().__init__()
@@ -82,7 +89,10 @@ class VAEAttention(nn.Module):
         q = self.q(n)[:, None]  # [b, 1(head), s, c]
         k = self.k(n)[:, None]
         v = self.v(n)[:, None]
-        o = ops.attention(q, k, v)[:, 0]
+        if self.flash and ops.attention_wide_supported(q, k, v):
+            o = ops.attention_wide(q, k, v)[:, 0]
+        else:
+            o = ops.attention(q, k, v)[:, 0]
         o = self.out(o).reshape(b, h, w, c).permute(0, 3, 1, 2)
         return x + o
 

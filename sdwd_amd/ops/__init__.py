@@ -482,6 +482,80 @@ def attention_bshd(
 
 
 # ---------------------------------------------------------------------------
+# wide head dims (256, 512): the VAE mid-block's flash kernel
+# ---------------------------------------------------------------------------
+_WIDE_DIMS = (256, 512)  # mirrors ext().attention_wide_supported
+
+
+def _rows16(t: torch.Tensor) -> bool:
+    """Unit stride in D and every row start 16-byte aligned."""
+    return (t.stride(-1) == 1 and t.data_ptr() % 16 == 0
+            and all(t.shape[i] == 1 or t.stride(i) % 8 == 0 for i in range(3)))
+
+
+def attention_wide_supported(q, k, v) -> bool:
+    """True when attention_wide runs its kernel on these [B,H,S,D] views: on
+    the GPU, bf16, head dim 256 or 512, unit stride in D and 16-byte-aligned
+    rows. The predicate callers route by."""
+    return bool(
+        q.dim() == k.dim() == v.dim() == 4
+        and q.is_cuda and k.is_cuda and v.is_cuda
+        and q.dtype == k.dtype == v.dtype == torch.bfloat16
+        and q.shape[-1] in _WIDE_DIMS
+        and k.shape == v.shape and k.shape[-1] == q.shape[-1]
+        and q.shape[:2] == k.shape[:2]
+        and q.shape[2] >= 1 and k.shape[2] >= 1
+        and _rows16(q) and _rows16(k) and _rows16(v)
+    )
+
+
+def attention_wide(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    scale: Optional[float] = None,
+) -> torch.Tensor:
+    """q [B,H,Sq,D], k/v [B,H,Sk,D] with D = 256 or 512 -> [B,H,Sq,D].
+
+    GPU: flash_wide_bf16_kernel (ops/hip/attention_wide.hip): no score
+    matrix in memory, v2's arithmetic (fp32 score scaling, one bf16 rounding
+    of P and of the output). Strided views ([B,S,H,D] permuted, slices of a
+    larger buffer) run with no copies. Anything the kernel does not take
+    raises ValueError naming the argument; nothing is composed silently.
+    CPU: the fp32 reference of attention().
+    """
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    if not q.is_cuda:
+        return attention(q, k, v, scale)
+    name = "attention_wide"
+    for nm, t in (("q", q), ("k", k), ("v", v)):
+        if t.dim() != 4:
+            raise ValueError(f"{name}: {nm} must be [B,H,S,D], got "
+                             f"{tuple(t.shape)}")
+        if not t.is_cuda:
+            raise ValueError(f"{name}: {nm} must be on the GPU like q")
+        if t.dtype != torch.bfloat16:
+            raise ValueError(f"{name}: {nm} must be bf16, got {t.dtype}")
+    if q.shape[-1] not in _WIDE_DIMS:
+        raise ValueError(f"{name}: q head dim {q.shape[-1]} has no wide "
+                         f"kernel (expected one of {_WIDE_DIMS})")
+    if k.shape != v.shape:
+        raise ValueError(f"{name}: k {tuple(k.shape)} and v {tuple(v.shape)} "
+                         "shapes differ")
+    if k.shape[-1] != q.shape[-1] or k.shape[:2] != q.shape[:2]:
+        raise ValueError(f"{name}: k {tuple(k.shape)} does not match q "
+                         f"{tuple(q.shape)} in batch, heads or head dim")
+    if q.shape[2] < 1 or k.shape[2] < 1:
+        raise ValueError(f"{name}: q and k need at least one row")
+    for nm, t in (("q", q), ("k", k), ("v", v)):
+        if not _rows16(t):
+            raise ValueError(f"{name}: {nm} needs unit stride in D and "
+                             "16-byte-aligned rows")
+    return ext().attention_wide(q, k, v, scale)
+
+
+# ---------------------------------------------------------------------------
 # Hypertile: self-attention inside rectangular windows of the token grid
 # ---------------------------------------------------------------------------
 def _window_extent(n: int, least: int) -> int:

@@ -15,6 +15,7 @@ static inline hipStream_t cur_stream() {
 #include "softmax.hip"
 #include "probe.hip"
 #include "attention.hip"
+#include "attention_wide.hip"
 #include "conv_v4.hip"
 #include "conv.hip"
 #include "conv_small.hip"
@@ -648,6 +649,45 @@ torch::Tensor attention_window_bshd(torch::Tensor q, torch::Tensor k,
   return flash_window_raw(q, k, v, scale, gh, gw, th, tw);
 }
 
+torch::Tensor attention_wide(torch::Tensor q, torch::Tensor k,
+                             torch::Tensor v, double scale) {
+  // [B,H,S,D] views, D = 256 or 512 (flash_wide_bf16_kernel). Everything an
+  // address is formed from is checked here; failures raise, nothing is
+  // composed silently
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4,
+              "attention_wide: q/k/v must be [B,H,S,D]");
+  TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda(),
+              "attention_wide: q/k/v must be on the GPU");
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16 &&
+                  k.scalar_type() == torch::kBFloat16 &&
+                  v.scalar_type() == torch::kBFloat16,
+              "attention_wide: q/k/v must be bf16");
+  const long D = q.size(3);
+  TORCH_CHECK(attention_wide_supported(D) && k.size(3) == D && v.size(3) == D,
+              "attention_wide: head dim must be 256 or 512, equal across "
+              "q/k/v");
+  TORCH_CHECK(k.sizes() == v.sizes(), "attention_wide: k/v shape mismatch");
+  TORCH_CHECK(q.size(0) == k.size(0) && q.size(1) == k.size(1),
+              "attention_wide: q and k differ in batch or heads");
+  TORCH_CHECK(q.size(0) >= 1 && q.size(1) >= 1 && q.size(2) >= 1 &&
+                  k.size(2) >= 1,
+              "attention_wide: empty q/k/v");
+  TORCH_CHECK(q.size(2) < (1L << 30) && k.size(2) < (1L << 30),
+              "attention_wide: Sq and Sk must be below 2^30");
+  TORCH_CHECK(q.size(0) * q.size(1) <= 65535, "attention_wide: batch * heads "
+              "= ", q.size(0) * q.size(1),
+              " exceeds the grid's y extent (65535)");
+  for (const auto &t : {q, k, v}) {
+    bool rows16 = t.stride(3) == 1 && ((uintptr_t)t.data_ptr()) % 16 == 0;
+    for (int i = 0; i < 3; ++i)
+      rows16 = rows16 && (t.size(i) == 1 || t.stride(i) % 8 == 0);
+    TORCH_CHECK(rows16,
+                "attention_wide: q/k/v need unit stride in D and "
+                "16-byte-aligned rows");
+  }
+  return flash_wide_raw(q, k, v, scale);
+}
+
 torch::Tensor attention_blend_bshd(torch::Tensor q, torch::Tensor k,
                                    torch::Tensor v, torch::Tensor w,
                                    torch::Tensor kv_index,
@@ -845,6 +885,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("k"), py::arg("v"), py::arg("gh"), py::arg("gw"),
         py::arg("th"), py::arg("tw"), py::arg("scale"));
   m.def("attention_window_plan", &attention_window_plan);
+  m.def("attention_wide", &attention_wide, py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("scale"));
+  m.def("attention_wide_plan", &attention_wide_plan);
+  m.def("attention_wide_supported", &attention_wide_supported);
   m.def("probe_mfma32", &probe_mfma32);
   m.def("probe_mfma16", &probe_mfma16);
   m.def("probe_tr16", &probe_tr16);

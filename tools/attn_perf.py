@@ -14,6 +14,9 @@ q, k, v and the output included, (4) the plain full-sequence call, (5) token
 merging at ratio 0.5 at the same shape (match, plan, merge, attention on the
 merged length), for orientation. The variants alternate inside each of
 --rounds rounds; the report is the median round and the min..max band.
+
+--wide times the VAE mid-block attention (D = 512, one head) two ways, the
+composed GEMM + softmax route and the wide flash kernel (wide_main).
 """
 import argparse
 import json
@@ -119,6 +122,52 @@ def window_main(args):
     return out
 
 
+def wide_main(args):
+    """--wide: the composed route (ops.attention) against the wide flash
+    kernel (ops.attention_wide) at the VAE mid-block shapes, D = 512, H = 1.
+    Both routes are warmed, then alternate inside each round; every round
+    times at least ~0.2 s of work per route. One JSON line per shape: median
+    and min..max per route, the kernel's useful TF/s, and at S = 16384 the
+    peak memory each route adds."""
+    D, H = 512, 1
+    for S in (1024, 4096, 16384):
+        for B in (1, 8):
+            tag = f"vae-mid-S{S}-B{B}"
+            if args.only and args.only not in tag:
+                continue
+            g = torch.Generator(device="cuda").manual_seed(S + B)
+            q, k, v = (torch.randn(B, H, S, D, device="cuda",
+                                   dtype=torch.bfloat16, generator=g)
+                       for _ in range(3))
+            assert ops.attention_wide_supported(q, k, v)
+            routes = {"composed": lambda: ops.attention(q, k, v),
+                      "wide": lambda: ops.attention_wide(q, k, v)}
+            res, iters = {}, {}
+            for name, fn in routes.items():
+                if S == 16384:
+                    torch.cuda.synchronize()
+                    torch.cuda.empty_cache()
+                    torch.cuda.reset_peak_memory_stats()
+                    base = torch.cuda.memory_allocated()
+                    fn()
+                    torch.cuda.synchronize()
+                    res[name + "_peak_mb"] = round(
+                        (torch.cuda.max_memory_allocated() - base) / 2**20, 1)
+                once = bench(fn, warm=2, it=2)
+                iters[name] = max(args.iters, min(200, int(0.2 / once) + 1))
+            times = {name: [] for name in routes}
+            for _ in range(args.rounds):
+                for name, fn in routes.items():
+                    times[name].append(bench(fn, warm=1, it=iters[name]))
+            for name, ts in times.items():
+                res[name] = _band(ts)
+            res["wide_tf"] = round(flops(B, H, S, S, D) /
+                                   (res["wide"]["median_ms"] * 1e-3) / 1e12, 1)
+            print(json.dumps({tag: res}), flush=True)
+            del q, k, v
+            torch.cuda.empty_cache()
+
+
 def bench(fn, warm=3, it=10):
     for _ in range(warm):
         fn()
@@ -139,14 +188,20 @@ def main():
                     help="flash kernel to time (default: follow SDWD_ATTN)")
     ap.add_argument("--window", action="store_true",
                     help="time Hypertile's windowed attention (five routes)")
+    ap.add_argument("--wide", action="store_true",
+                    help="time the VAE mid-block (D=512): composed route "
+                         "against the wide flash kernel")
     ap.add_argument("--batch", type=int, default=128,
                     help="--window: batch rows (headline: 64 images x CFG)")
     ap.add_argument("--rounds", type=int, default=5,
-                    help="--window: alternating rounds per shape")
+                    help="--window / --wide: alternating rounds per shape")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "GPU required"
     if args.window:
         window_main(args)
+        return
+    if args.wide:
+        wide_main(args)
         return
     results = {}
     for tag, B, H, Sq, Sk, D in SHAPES:
