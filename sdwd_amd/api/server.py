@@ -955,6 +955,23 @@ def create_app(engine: Optional[LocalEngine] = None,
         }
         m, aa = mode_map.get(mode, ("bilinear", True))
         x = img.permute(2, 0, 1)[None].float()
+        if mode not in mode_map:
+            from ..models.registry import find_upscaler, load_upscaler
+
+            name = find_upscaler(str(body.get("upscaler_1")))
+            if name is not None:
+                # a model from SDWD_UPSCALER_DIR: 4x once, then the Lanczos
+                # entry resizes to the requested size, as hires fix does
+                from ..models.esrgan import upscale_image
+
+                pipe = next(iter(engine.pipes.values()))
+                net = load_upscaler(name, pipe.device, pipe.dtype)
+                try:
+                    x = upscale_image(net, x / 255.0) * 255.0
+                except ValueError as exc:
+                    raise HTTPException(422, str(exc))
+                scale = scale / 4.0
+                m, aa = mode_map["lanczos"]
         kwargs: Dict[str, Any] = {"mode": m}
         if aa:
             kwargs["antialias"] = True
@@ -993,10 +1010,18 @@ def create_app(engine: Optional[LocalEngine] = None,
     # -- static enumerations sdwui GUIs query at startup ---------------------
     @app.get("/sdapi/v1/upscalers")
     def upscalers():
-        return [
+        from ..models.registry import available_upscalers
+
+        out = [
             {"name": n, "model_name": None, "model_path": None, "scale": 4}
             for n in ("None", "Nearest", "Bilinear", "Bicubic", "Lanczos")
         ]
+        # ESRGAN-family models found in SDWD_UPSCALER_DIR
+        out += [
+            {"name": n, "model_name": n, "model_path": path, "scale": 4}
+            for n, path in sorted(available_upscalers().items())
+        ]
+        return out
 
     @app.get("/sdapi/v1/latent-upscale-modes")
     def latent_upscale_modes():

@@ -400,6 +400,67 @@ def load_vae_into(bundle, name: str) -> Dict[str, list]:
     return report
 
 
+_UPSCALER_FILES: Dict[str, str] = {}
+_upscaler_cache: Dict[tuple, "object"] = {}
+
+
+def upscaler_dir() -> str:
+    import os
+
+    return os.environ.get("SDWD_UPSCALER_DIR", "upscalers")
+
+
+def refresh_upscaler_files(dirpath: Optional[str] = None) -> list:
+    """Scan the upscaler directory for *.safetensors ESRGAN-family models
+    (the host's ESRGAN / RealESRGAN model folders). The file stem is the
+    upscaler's name as hr_upscaler / upscaler_1 give it."""
+    import os
+
+    global _UPSCALER_FILES
+    d = dirpath or upscaler_dir()
+    found: Dict[str, str] = {}
+    if os.path.isdir(d):
+        for fn in sorted(os.listdir(d)):
+            if fn.endswith(".safetensors"):
+                found[os.path.splitext(fn)[0]] = os.path.join(d, fn)
+    _UPSCALER_FILES = found
+    return sorted(found)
+
+
+def available_upscalers() -> Dict[str, str]:
+    """name -> path of the model upscalers found by a fresh scan."""
+    refresh_upscaler_files()
+    return dict(_UPSCALER_FILES)
+
+
+def find_upscaler(name: Optional[str]) -> Optional[str]:
+    """The found upscaler whose name matches `name` case-insensitively, or
+    None (the caller then keeps its model-free route)."""
+    key = (name or "").strip().lower()
+    if not key:
+        return None
+    for cand in available_upscalers():
+        if cand.lower() == key:
+            return cand
+    return None
+
+
+def load_upscaler(name: str, device="cpu", dtype: Optional[torch.dtype] = None):
+    """The named upscaler (models/esrgan.py RRDBNet) on `device`, cached per
+    (file, device, dtype)."""
+    from .esrgan import load_esrgan
+
+    found = find_upscaler(name)
+    if found is None:
+        raise KeyError(f"unknown upscaler '{name}'")
+    key = (_UPSCALER_FILES[found], str(device), str(dtype))
+    if key not in _upscaler_cache:
+        log.info("loading upscaler '%s'", key[0])
+        _upscaler_cache[key] = load_esrgan(key[0]).to(device=device,
+                                                      dtype=dtype)
+    return _upscaler_cache[key]
+
+
 def load_model(
     name: str, device="cpu", dtype: Optional[torch.dtype] = None,
     cache: bool = True,
@@ -458,6 +519,7 @@ def load_controlnet(name: str = "controlnet-sd15", device="cpu", dtype=None):
 def clear_cache() -> None:
     _cache.clear()
     _cn_cache.clear()
+    _upscaler_cache.clear()
 
 
 # -- checkpoint files (ref C13 synced checkpoints by NAME over /options;

@@ -1304,6 +1304,165 @@ def ups2x_conv3x3(
 
 
 # ---------------------------------------------------------------------------
+# dense-block 3x3 conv on channel slices (the RRDBNet trunk, models/esrgan.py)
+# ---------------------------------------------------------------------------
+def _dense_nhwc(t: torch.Tensor) -> bool:
+    """A channel slice of an NHWC buffer the dense kernel can address: unit
+    channel stride, rows of W pixels, pixel and image strides that are
+    multiples of 8 elements, a 16-byte-aligned base, offsets below 2^31."""
+    n, c, h, w = t.shape
+    ld = t.stride(3)
+    return bool(
+        t.stride(1) == 1 and ld >= c and ld % 8 == 0
+        and t.stride(2) == w * ld and t.stride(0) % 8 == 0
+        and (n == 1 or t.stride(0) >= h * w * ld)
+        and t.data_ptr() % 16 == 0 and h * w * ld < 2 ** 31
+    )
+
+
+def _dense_overlap(out: torch.Tensor, t: torch.Tensor) -> str:
+    """How out's channels relate to t's when both live in one storage:
+    "disjoint", "identical", or "overlap" (anything else)."""
+    if out.untyped_storage().data_ptr() != t.untyped_storage().data_ptr():
+        return "disjoint"
+
+    def extent(v):
+        return ((v.shape[0] - 1) * v.stride(0) + (v.shape[2] - 1) * v.stride(2)
+                + (v.shape[3] - 1) * v.stride(3) + v.shape[1])
+
+    y0, t0 = out.storage_offset(), t.storage_offset()
+    if y0 + extent(out) <= t0 or t0 + extent(t) <= y0:
+        return "disjoint"
+    ld = out.stride(3)
+    if ld <= 0 or (t.stride(3), t.stride(2), t.stride(0)) != (
+            ld, out.stride(2), out.stride(0)):
+        return "overlap"
+    cy, ct = y0 % ld, t0 % ld
+    if (y0 - cy != t0 - ct or cy + out.shape[1] > ld
+            or ct + t.shape[1] > ld):
+        return "overlap"
+    if cy + out.shape[1] <= ct or ct + t.shape[1] <= cy:
+        return "disjoint"
+    if cy == ct and out.shape[1] == t.shape[1]:
+        return "identical"
+    return "overlap"
+
+
+def conv3x3_dense_supported(x, w_prep, out) -> bool:
+    """True when conv3x3_dense runs conv3x3_dense_bf16_kernel on these views:
+    bf16 on the GPU, Cin % 32 == 0 in [64, 256], Cout 32 or 64, N <= 65535,
+    NHWC channel slices (unit channel stride, pixel strides % 8 == 0,
+    16-byte-aligned bases), w_prep contiguous. The routing predicate."""
+    return bool(
+        x.is_cuda and out.is_cuda and w_prep.is_cuda
+        and x.dtype == out.dtype == w_prep.dtype == torch.bfloat16
+        and x.dim() == out.dim() == w_prep.dim() == 4
+        and x.shape[1] % 32 == 0 and 64 <= x.shape[1] <= 256
+        and out.shape[1] in (32, 64)
+        and 1 <= x.shape[0] <= 65535 and x.shape[2] >= 1 and x.shape[3] >= 1
+        and w_prep.is_contiguous() and w_prep.data_ptr() % 16 == 0
+        and _dense_nhwc(x) and _dense_nhwc(out)
+    )
+
+
+def conv3x3_dense(
+    x: torch.Tensor,
+    w_prep: torch.Tensor,
+    bias: Optional[torch.Tensor],
+    out: torch.Tensor,
+    *,
+    alpha: float = 1.0,
+    res1: Optional[torch.Tensor] = None,
+    beta: float = 1.0,
+    res2: Optional[torch.Tensor] = None,
+    lrelu: Optional[float] = None,
+) -> torch.Tensor:
+    """out <- act(alpha * (conv3x3(x, w) + bias) + beta * res1 + res2), pad
+    1, stride 1; act is LeakyReLU(lrelu) when lrelu is given. Written in
+    place into `out`, which is returned.
+
+    x, out, res1, res2 are [N, C, H, W] views with unit channel stride:
+    channel slices of channels_last buffers (buf[:, :96], buf[:, 96:128]),
+    possibly of ONE buffer, so a dense block runs with no concatenation. out
+    must not share channels with x; a residual is disjoint from out or is
+    exactly out's slice. w_prep is [Cout, 3, 3, Cin].
+
+    GPU, conv3x3_dense_supported(x, w_prep, out): conv3x3_dense_bf16_kernel
+    (ops/hip/conv_dense.hip), fp32 accumulate, one bf16 rounding. CPU, or
+    when the predicate is false: the same formula with F.conv2d (fp32 math
+    for bf16) copied into out. A bad argument raises ValueError naming it.
+    """
+    name = "conv3x3_dense"
+    for nm, t in (("x", x), ("w_prep", w_prep), ("out", out)):
+        if not torch.is_tensor(t) or t.dim() != 4:
+            raise ValueError(f"{name}: {nm} must be a 4-d tensor")
+    n, cin, h, w = x.shape
+    cout = out.shape[1]
+    if min(n, cin, h, w) < 1:
+        raise ValueError(f"{name}: x must be non-empty, got {tuple(x.shape)}")
+    if tuple(w_prep.shape) != (cout, 3, 3, cin):
+        raise ValueError(
+            f"{name}: w_prep must be [Cout,3,3,Cin] = {(cout, 3, 3, cin)}, "
+            f"got {tuple(w_prep.shape)}"
+        )
+    if bias is not None and bias.numel() != cout:
+        raise ValueError(f"{name}: bias must hold {cout} values, got "
+                         f"{bias.numel()}")
+    views = [("out", out), ("res1", res1), ("res2", res2)]
+    for nm, t in views:
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or tuple(t.shape) != (n, cout, h, w):
+            raise ValueError(
+                f"{name}: {nm} must be {(n, cout, h, w)}, got "
+                f"{tuple(t.shape) if torch.is_tensor(t) else type(t)}"
+            )
+    for nm, t in (("w_prep", w_prep), ("bias", bias)) + tuple(views):
+        if t is None:
+            continue
+        if t.device != x.device:
+            raise ValueError(f"{name}: {nm} is on {t.device}, x on {x.device}")
+        if nm != "bias" and t.dtype != x.dtype:
+            raise ValueError(f"{name}: {nm} is {t.dtype}, x is {x.dtype}")
+    for nm, t in (("x", x),) + tuple(views):
+        if t is not None and t.stride(1) != 1:
+            raise ValueError(f"{name}: {nm} needs unit channel stride "
+                             "(a channel slice of a channels_last buffer)")
+    if _dense_overlap(out, x) != "disjoint":
+        raise ValueError(f"{name}: out shares channels with x")
+    for nm, t in views[1:]:
+        if t is not None and _dense_overlap(out, t) == "overlap":
+            raise ValueError(f"{name}: out partly overlaps {nm}; a residual "
+                             "is disjoint from out or exactly its slice")
+    if lrelu is not None and not isinstance(lrelu, (int, float)):
+        raise ValueError(f"{name}: lrelu must be a slope or None")
+
+    native = conv3x3_dense_supported(x, w_prep, out) and all(
+        t is None or _dense_nhwc(t) for t in (res1, res2)
+    )
+    if native:
+        return ext().conv3x3_dense(
+            x, w_prep, bias, out, float(alpha), res1, float(beta), res2,
+            lrelu is not None, float(lrelu or 0.0),
+        )
+    wide = x.dtype == torch.bfloat16
+    up = (lambda t: t.float()) if wide else (lambda t: t)
+    y = F.conv2d(
+        up(x), up(w_prep).permute(0, 3, 1, 2),
+        None if bias is None else bias.to(up(x).dtype), padding=1,
+    )
+    y = y * float(alpha)
+    if res1 is not None:
+        y = y + float(beta) * up(res1)
+    if res2 is not None:
+        y = y + up(res2)
+    if lrelu is not None:
+        y = F.leaky_relu(y, float(lrelu))
+    out.copy_(y)
+    return out
+
+
+# ---------------------------------------------------------------------------
 # timestep embedding (sinusoidal)
 # ---------------------------------------------------------------------------
 def timestep_embedding(

@@ -19,6 +19,7 @@ static inline hipStream_t cur_stream() {
 #include "conv_v4.hip"
 #include "conv.hip"
 #include "conv_small.hip"
+#include "conv_dense.hip"
 #include "rng.hip"
 #include "tome.hip"
 
@@ -909,4 +910,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("wrap_w") = false, py::arg("w_fold") = py::none(),
         py::arg("fold") = true);
   m.def("conv3x3_small_supported", &conv3x3_small_supported);
+  m.def("conv3x3_dense", &conv3x3_dense, py::arg("x"), py::arg("w_prep"),
+        py::arg("bias"), py::arg("out"), py::arg("alpha"), py::arg("res1"),
+        py::arg("beta"), py::arg("res2"), py::arg("lrelu"), py::arg("slope"));
+  m.def("conv3x3_dense_supported_widths", &conv3x3_dense_supported_widths);
 }

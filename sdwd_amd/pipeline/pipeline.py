@@ -574,11 +574,21 @@ class StableDiffusionPipeline:
         """Pixel-space hires handoff (sdwui non-"Latent" hr_upscalers):
         decode the base latents, upscale the uint8 pixels (the PIL round
         trip sdwui performs), re-encode per image (shard-invariant,
-        seeded). Model-based upscaler names fall back to
-        bicubic-antialiased with a warning."""
+        seeded). A name found in SDWD_UPSCALER_DIR runs that ESRGAN-family
+        model (models/esrgan.py) on the decoded image; any other model-based
+        name falls back to bicubic-antialiased with a warning."""
         key = (req.hr_upscaler or "").lower()
         m, aa = _PIXEL_HR_MODES.get(key, ("bicubic", True))
+        model = None
         if key not in _PIXEL_HR_MODES:
+            from ..models.registry import find_upscaler, load_upscaler
+
+            if find_upscaler(req.hr_upscaler) is not None:
+                # a model from SDWD_UPSCALER_DIR: 4x once, then down (or up)
+                # to the target with the Lanczos entry, as the host does
+                model = load_upscaler(req.hr_upscaler, self.device, self.dtype)
+                m, aa = _PIXEL_HR_MODES["lanczos"]
+        if key not in _PIXEL_HR_MODES and model is None:
             log.warning(
                 "hr upscaler %r needs model weights that cannot ship "
                 "offline; using bicubic-antialiased pixels", req.hr_upscaler,
@@ -595,8 +605,13 @@ class StableDiffusionPipeline:
             img8 = (
                 ((img.float() + 1.0) * 127.5).clamp(0, 255).to(torch.uint8)
             )
+            src = img8.float()
+            if model is not None:
+                src = model(
+                    (src / 255.0).to(self.dtype)
+                ).float().clamp(0, 1) * 255.0
             up = torch.nn.functional.interpolate(
-                img8.float(), size=(th * f, tw * f), mode=m, **kwargs
+                src, size=(th * f, tw * f), mode=m, **kwargs
             )
             outs.append(
                 up.clamp(0, 255).to(torch.uint8)[0].permute(1, 2, 0).cpu()
