@@ -446,9 +446,11 @@ def find_upscaler(name: Optional[str]) -> Optional[str]:
 
 
 def load_upscaler(name: str, device="cpu", dtype: Optional[torch.dtype] = None):
-    """The named upscaler (models/esrgan.py RRDBNet) on `device`, cached per
+    """The named upscaler (models/esrgan.py RRDBNet or models/swinir.py
+    SwinIR, told apart by the file's tensor names) on `device`, cached per
     (file, device, dtype)."""
     from .esrgan import load_esrgan
+    from .swinir import is_swinir_state_dict, load_swinir
 
     found = find_upscaler(name)
     if found is None:
@@ -456,8 +458,14 @@ def load_upscaler(name: str, device="cpu", dtype: Optional[torch.dtype] = None):
     key = (_UPSCALER_FILES[found], str(device), str(dtype))
     if key not in _upscaler_cache:
         log.info("loading upscaler '%s'", key[0])
-        _upscaler_cache[key] = load_esrgan(key[0]).to(device=device,
-                                                      dtype=dtype)
+        load = load_esrgan
+        if key[0].endswith(".safetensors"):
+            from safetensors import safe_open
+
+            with safe_open(key[0], framework="pt") as f:
+                if is_swinir_state_dict(f.keys()):
+                    load = load_swinir
+        _upscaler_cache[key] = load(key[0]).to(device=device, dtype=dtype)
     return _upscaler_cache[key]
 
 

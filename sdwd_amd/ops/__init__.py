@@ -556,6 +556,146 @@ def attention_wide(
 
 
 # ---------------------------------------------------------------------------
+# shifted-window attention with a relative-position bias (SwinIR)
+# ---------------------------------------------------------------------------
+SWIN_WINDOW = 8
+SWIN_DPAD = 32  # the kernel's head row: 30 channels padded by the model
+
+
+def _swin_kernel_reason(qkv: torch.Tensor, bias: torch.Tensor) -> Optional[str]:
+    """Why swin_attn_bf16_kernel does not take these (shape-checked)
+    arguments, or None when it does."""
+    if not (qkv.is_cuda and bias.is_cuda and qkv.device == bias.device):
+        return "qkv and bias must be on the same GPU"
+    if qkv.dtype != torch.bfloat16:
+        return f"qkv must be bf16, got {qkv.dtype}"
+    if bias.dtype != torch.float32:
+        return f"bias must be fp32, got {bias.dtype}"
+    if not bias.is_contiguous() or bias.data_ptr() % 16:
+        return "bias must be contiguous and 16-byte aligned"
+    if qkv.shape[5] != SWIN_DPAD:
+        return (f"head dim {qkv.shape[5]} must be padded to Dp = "
+                f"{SWIN_DPAD} (zero channels) by the caller")
+    if qkv.stride(5) != 1 or qkv.data_ptr() % 16 or any(
+            qkv.shape[i] != 1 and (qkv.stride(i) % 8 or qkv.stride(i) < 0)
+            for i in range(5)):
+        return ("qkv needs unit innermost stride and 16-byte-aligned head "
+                "rows (outer strides multiples of 8)")
+    return None
+
+
+def _swin_check(qkv: torch.Tensor, bias: torch.Tensor, shift: int) -> None:
+    name = "attention_swin"
+    if qkv.dim() != 6 or qkv.shape[3] != 3:
+        raise ValueError(f"{name}: qkv must be [B, H, W, 3, heads, Dp], got "
+                         f"{tuple(qkv.shape)}")
+    b, h, w, _, heads, _ = qkv.shape
+    if b < 1 or heads < 1 or h < 1 or w < 1 or h % SWIN_WINDOW or w % SWIN_WINDOW:
+        raise ValueError(f"{name}: the token grid {h} x {w} must be a "
+                         f"multiple of the window ({SWIN_WINDOW})")
+    n = SWIN_WINDOW * SWIN_WINDOW
+    if tuple(bias.shape) != (heads, n, n):
+        raise ValueError(f"{name}: bias must be [heads, {n}, {n}] = "
+                         f"[{heads}, {n}, {n}] (window {SWIN_WINDOW}), got "
+                         f"{tuple(bias.shape)}")
+    if shift not in (0, SWIN_WINDOW // 2):
+        raise ValueError(f"{name}: shift must be 0 or {SWIN_WINDOW // 2}, "
+                         f"got {shift}")
+    if not (qkv.is_floating_point() and bias.is_floating_point()):
+        raise ValueError(f"{name}: qkv and bias must be floating point")
+
+
+def attention_swin_supported(qkv: torch.Tensor, bias: torch.Tensor) -> bool:
+    """True when attention_swin runs swin_attn_bf16_kernel on these
+    arguments: qkv a bf16 [B, H, W, 3, heads, 32] GPU view with unit
+    innermost stride and 16-byte-aligned head rows, H and W multiples of 8,
+    bias a contiguous, 16-byte-aligned fp32 [heads, 64, 64] on the same
+    GPU."""
+    try:
+        _swin_check(qkv, bias, 0)
+    except ValueError:
+        return False
+    return _swin_kernel_reason(qkv, bias) is None
+
+
+def _swin_region_mask(h: int, w: int, shift: int, device) -> torch.Tensor:
+    """[windows, 64, 64]: -100 where query and key lie in different regions
+    of the shifted frame, built from the three row and three column slices."""
+    ws = SWIN_WINDOW
+    img = torch.zeros(h, w, device=device)
+    cnt = 0
+    for hs in (slice(0, -ws), slice(-ws, -shift), slice(-shift, None)):
+        for wsl in (slice(0, -ws), slice(-ws, -shift), slice(-shift, None)):
+            img[hs, wsl] = cnt
+            cnt += 1
+    win = img.view(h // ws, ws, w // ws, ws).permute(0, 2, 1, 3)
+    win = win.reshape(-1, ws * ws)
+    diff = win[:, None, :] - win[:, :, None]
+    return torch.zeros_like(diff).masked_fill(diff != 0, -100.0)
+
+
+def _attention_swin_torch(qkv, bias, scale: float, shift: int) -> torch.Tensor:
+    """The literal definition: roll, partition, bias and slice-built mask,
+    softmax, reverse, roll back. Any head dim, any float dtype (bf16 and
+    fp16 compute in fp32)."""
+    ws = SWIN_WINDOW
+    b, h, w, _, heads, d = qkv.shape
+    cdt = qkv.dtype if qkv.dtype in (torch.float32, torch.float64) \
+        else torch.float32
+    x = qkv.to(cdt)
+    if shift:
+        x = torch.roll(x, shifts=(-shift, -shift), dims=(1, 2))
+    # partition: [B * windows, 64, 3, heads, d] -> q, k, v [B*win, heads, 64, d]
+    x = x.reshape(b, h // ws, ws, w // ws, ws, 3, heads, d)
+    x = x.permute(0, 1, 3, 2, 4, 5, 6, 7).reshape(-1, ws * ws, 3, heads, d)
+    q, k, v = x.permute(2, 0, 3, 1, 4).unbind(0)
+    attn = (q * scale) @ k.transpose(-2, -1) + bias.to(cdt)[None]
+    if shift:
+        mask = _swin_region_mask(h, w, shift, qkv.device).to(cdt)
+        nw = mask.shape[0]
+        attn = attn.view(b, nw, heads, ws * ws, ws * ws) + mask[None, :, None]
+        attn = attn.view(-1, heads, ws * ws, ws * ws)
+    out = torch.softmax(attn, dim=-1) @ v           # [B*win, heads, 64, d]
+    out = out.transpose(1, 2).reshape(b, h // ws, w // ws, ws, ws, heads * d)
+    out = out.permute(0, 1, 3, 2, 4, 5).reshape(b, h, w, heads * d)
+    if shift:
+        out = torch.roll(out, shifts=(shift, shift), dims=(1, 2))
+    return out.to(qkv.dtype)
+
+
+def attention_swin(
+    qkv: torch.Tensor,
+    bias: torch.Tensor,
+    scale: float,
+    shift: int = 0,
+    native: bool = True,
+) -> torch.Tensor:
+    """SwinIR's (shifted-)window attention over an un-partitioned token grid.
+
+    qkv [B, H, W, 3, heads, Dp] is the QKV projection of the grid (a view of
+    the GEMM output is fine), bias [heads, 64, 64] the gathered relative
+    position bias; windows are 8 x 8, shift is 0 or 4. Returns
+    [B, H, W, heads * Dp] with every query's row at its un-shifted token, so
+    the caller rolls, partitions and reverses nothing.
+
+    bf16 qkv on the GPU runs swin_attn_bf16_kernel
+    (ops/hip/attention_swin.hip) and must satisfy its contract (Dp = 32,
+    contiguous fp32 bias, aligned head rows): what it does not take raises
+    ValueError with the reason, nothing is composed silently. CPU tensors,
+    other dtypes and native=False take the literal torch definition, which
+    the model's reference route uses.
+    """
+    shift = int(shift)
+    _swin_check(qkv, bias, shift)
+    if native and qkv.is_cuda and qkv.dtype == torch.bfloat16:
+        why = _swin_kernel_reason(qkv, bias)
+        if why is not None:
+            raise ValueError(f"attention_swin: {why}")
+        return ext().attention_swin(qkv, bias, float(scale), shift)
+    return _attention_swin_torch(qkv, bias, float(scale), shift)
+
+
+# ---------------------------------------------------------------------------
 # Hypertile: self-attention inside rectangular windows of the token grid
 # ---------------------------------------------------------------------------
 def _window_extent(n: int, least: int) -> int:

@@ -2,7 +2,8 @@
 //
 // Three kernels built from one set of pieces.
 //
-// Shared by all three (the helpers below, each written once):
+// Shared by all three (the helpers below and common.h's crow, pack_bf16 and
+// p_relayout, each written once):
 //  * workgroup = 4 waves; each wave owns QS 32-row q-subtiles, the WG shares
 //    K/V tiles of KVB = 64 keys staged in LDS (AttnGeom<DPAD>).
 //  * swapped QK^T: S^T = mfma(K_frag, Q_frag) so each lane holds the scores
@@ -50,15 +51,6 @@
 #include <type_traits>
 #include <utility>
 
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-  union {
-    __hip_bfloat162 h2;
-    unsigned u;
-  } cvt;
-  cvt.h2 = __hip_bfloat162(__float2bfloat16(lo), __float2bfloat16(hi));
-  return cvt.u;
-}
-
 struct AttnStrides {
   long qb, qh, qr;  // batch, head, row strides (elements)
   long kb, kh, kr;
@@ -102,12 +94,6 @@ constexpr int v3_qs(int dpad) { return dpad <= 96 ? 2 : 1; }
 constexpr int blend_qs(int dpad) { return dpad <= 32 ? 2 : 1; }
 constexpr int blend_min_blocks(int dpad) { return dpad <= 96 ? 2 : 1; }
 
-// C layout of the 32x32 MFMA: the row that accumulator register r holds in
-// half-wave `half` (the column is lane % 32)
-__device__ __forceinline__ int crow(int r, int half) {
-  return (r & 3) + 8 * (r >> 2) + 4 * half;
-}
-
 // Q fragments of one 32-row q-subtile, read once; qq is this lane's q row.
 // B-frag of mfma(K,Q): lane holds Q[q=lq][d = c*16 + 8*half + i]. Rows past
 // Sq re-read the last row (never stored); 8-groups beyond D are zero. FOLD
@@ -131,22 +117,6 @@ __device__ __forceinline__ void load_q_frags(bf16x8 (&qf)[NC],
     }
     qf[c] = qv;
   }
-}
-
-// one S^T[32k, 32q] score sub-tile -> the two PV A-fragments (16 keys each)
-__device__ __forceinline__ void p_relayout(const f32x16 &s, bf16x8 &pa0,
-                                           bf16x8 &pa1) {
-  unsigned pk[8];
-#pragma unroll
-  for (int t = 0; t < 8; ++t) pk[t] = pack_bf16(s[2 * t], s[2 * t + 1]);
-  auto r0 = __builtin_amdgcn_permlane32_swap(pk[0], pk[2], false, false);
-  auto r1 = __builtin_amdgcn_permlane32_swap(pk[1], pk[3], false, false);
-  unsigned frag[4] = {r0[0], r1[0], r0[1], r1[1]};
-  pa0 = *(bf16x8 *)frag;
-  auto r2 = __builtin_amdgcn_permlane32_swap(pk[4], pk[6], false, false);
-  auto r3 = __builtin_amdgcn_permlane32_swap(pk[5], pk[7], false, false);
-  unsigned frag1[4] = {r2[0], r3[0], r2[1], r3[1]};
-  pa1 = *(bf16x8 *)frag1;
 }
 
 // epilogue (v2, blend) of register r of the q-subtile whose first row is

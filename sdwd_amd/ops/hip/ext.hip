@@ -16,6 +16,7 @@ static inline hipStream_t cur_stream() {
 #include "probe.hip"
 #include "attention.hip"
 #include "attention_wide.hip"
+#include "attention_swin.hip"
 #include "conv_v4.hip"
 #include "conv.hip"
 #include "conv_small.hip"
@@ -689,6 +690,45 @@ torch::Tensor attention_wide(torch::Tensor q, torch::Tensor k,
   return flash_wide_raw(q, k, v, scale);
 }
 
+torch::Tensor attention_swin(torch::Tensor qkv, torch::Tensor bias,
+                             double scale, long shift) {
+  // qkv [B, H, W, 3, heads, 32] view, bias [heads, 64, 64] fp32
+  // (swin_attn_bf16_kernel). Everything an address is formed from is checked
+  // here; failures raise, nothing is composed silently
+  TORCH_CHECK(qkv.dim() == 6 && qkv.size(3) == 3 && qkv.size(5) == 32,
+              "attention_swin: qkv must be [B, H, W, 3, heads, 32]");
+  TORCH_CHECK(qkv.is_cuda() && bias.is_cuda() &&
+                  qkv.get_device() == bias.get_device(),
+              "attention_swin: qkv and bias must be on the same GPU");
+  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16,
+              "attention_swin: qkv must be bf16");
+  TORCH_CHECK(bias.scalar_type() == torch::kFloat32,
+              "attention_swin: bias must be fp32");
+  const long B = qkv.size(0), H = qkv.size(1), W = qkv.size(2),
+             heads = qkv.size(4);
+  TORCH_CHECK(B >= 1 && heads >= 1 && H >= 8 && W >= 8 && H % 8 == 0 &&
+                  W % 8 == 0,
+              "attention_swin: the token grid ", H, " x ", W,
+              " must be a positive multiple of the window (8)");
+  TORCH_CHECK(bias.dim() == 3 && bias.size(0) == heads && bias.size(1) == 64 &&
+                  bias.size(2) == 64 && bias.is_contiguous() &&
+                  ((uintptr_t)bias.data_ptr()) % 16 == 0,
+              "attention_swin: bias must be a contiguous, 16-byte-aligned "
+              "[heads, 64, 64]");
+  TORCH_CHECK(shift == 0 || shift == 4, "attention_swin: shift must be 0 or 4");
+  TORCH_CHECK(heads <= 65535 && B * H * W * heads * 32 < (1L << 40) &&
+                  B * (H / 8) * (W / 8) < (1L << 31),
+              "attention_swin: problem too large");
+  bool rows16 = qkv.stride(5) == 1 && ((uintptr_t)qkv.data_ptr()) % 16 == 0;
+  for (int i = 0; i < 5; ++i)
+    rows16 = rows16 && (qkv.size(i) == 1 || qkv.stride(i) % 8 == 0) &&
+             qkv.stride(i) >= 0;
+  TORCH_CHECK(rows16,
+              "attention_swin: qkv needs unit stride in the head dim and "
+              "16-byte-aligned head rows");
+  return swin_attn_raw(qkv, bias, scale, shift);
+}
+
 torch::Tensor attention_blend_bshd(torch::Tensor q, torch::Tensor k,
                                    torch::Tensor v, torch::Tensor w,
                                    torch::Tensor kv_index,
@@ -890,6 +930,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("v"), py::arg("scale"));
   m.def("attention_wide_plan", &attention_wide_plan);
   m.def("attention_wide_supported", &attention_wide_supported);
+  m.def("attention_swin", &attention_swin, py::arg("qkv"), py::arg("bias"),
+        py::arg("scale"), py::arg("shift"));
+  m.def("attention_swin_plan", &attention_swin_plan);
   m.def("probe_mfma32", &probe_mfma32);
   m.def("probe_mfma16", &probe_mfma16);
   m.def("probe_tr16", &probe_tr16);

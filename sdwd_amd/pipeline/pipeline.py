@@ -574,9 +574,10 @@ class StableDiffusionPipeline:
         """Pixel-space hires handoff (sdwui non-"Latent" hr_upscalers):
         decode the base latents, upscale the uint8 pixels (the PIL round
         trip sdwui performs), re-encode per image (shard-invariant,
-        seeded). A name found in SDWD_UPSCALER_DIR runs that ESRGAN-family
-        model (models/esrgan.py) on the decoded image; any other model-based
-        name falls back to bicubic-antialiased with a warning."""
+        seeded). A name found in SDWD_UPSCALER_DIR runs that model (RRDBNet,
+        models/esrgan.py, or SwinIR, models/swinir.py) on the decoded image;
+        any other model-based name falls back to bicubic-antialiased with a
+        warning."""
         key = (req.hr_upscaler or "").lower()
         m, aa = _PIXEL_HR_MODES.get(key, ("bicubic", True))
         model = None
