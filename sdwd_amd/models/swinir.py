@@ -10,13 +10,16 @@ and the 64-channel upsampling tail of RRDBNet.
 On a bf16 GPU the tokens stay one [B, H, W, C] tensor from conv_first to the
 tail. A Swin block is: ops.layer_norm, the QKV GEMM, ops.attention_swin on the
 GEMM's output viewed as [B, H, W, 3, heads, 32], the proj GEMM,
-ops.add_layer_norm (residual + norm2), the MLP, and ops.add_layer_norm again
-where the next block's norm1 follows. Nothing is rolled, partitioned, masked
-or permuted. Each head's 30 q/k/v rows are zero-padded to 32 once per weight
-version so a head row is 64 bytes: padded q/k channels add 0 to every score
-and padded v channels meet zero proj columns. The GEMMs, the MLP's GELU and
-the 3x3 convs at 180 / 240 channels (Cin % 64 != 0, one per six attention
-blocks) stay on the library.
+ops.add_layer_norm (residual + norm2), and ops.swin_mlp: fc1, GELU, fc2, the
+residual and the next block's norm1 in one kernel (Mlp.fused). Nothing is
+rolled, partitioned, masked or permuted. Each head's 30 q/k/v rows are
+zero-padded to 32 once per weight version so a head row is 64 bytes: padded
+q/k channels add 0 to every score and padded v channels meet zero proj
+columns; the MLP's weights are zero-padded once the same way
+(ops.swin_mlp_prepare). The QKV and proj GEMMs and the 3x3 convs at 180 / 240
+channels (Cin % 64 != 0, one per six attention blocks) stay on the library,
+and so does the MLP at an embed width the kernel has no instantiation for
+(no multiple of 4, or above 256), which runs composed as with Mlp.fused off.
 """
 from __future__ import annotations
 
@@ -127,10 +130,26 @@ class WindowAttention(nn.Module):
 
 
 class Mlp(nn.Module):
+    # the native route runs fc1 + GELU + fc2 + residual + the following norm
+    # as one ops.swin_mlp call; False keeps the composed route
+    fused = True
+
     def __init__(self, dim: int, hidden: int):
         super().__init__()
         self.fc1 = nn.Linear(dim, hidden)
         self.fc2 = nn.Linear(hidden, dim)
+        self._prep_cache = None
+
+    def prepared(self):
+        """ops.swin_mlp_prepare of fc1 and fc2 (zero-padded weights, fp32
+        biases), rebuilt when a source tensor changes (like
+        WindowAttention.prepared)."""
+        src = (self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
+        key = tuple((t.data_ptr(), t._version, t.dtype) for t in src)
+        if self._prep_cache is None or self._prep_cache[0] != key:
+            with torch.no_grad():
+                self._prep_cache = (key,) + tuple(ops.swin_mlp_prepare(*src))
+        return self._prep_cache[1:]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self.fc2(F.gelu(self.fc1(x)))
@@ -264,15 +283,24 @@ class SwinIR(nn.Module):
     def _blocks_native(self, t: torch.Tensor, blocks) -> torch.Tensor:
         """t [B, H, W, C] through a group's Swin blocks. n is norm1(t) of the
         block about to run: ops.layer_norm for the first, the second output
-        of the previous block's closing ops.add_layer_norm for the rest."""
+        of the previous block's closing ops.swin_mlp (ops.add_layer_norm
+        with Mlp.fused off, or at an embed width that is no multiple of 4 or
+        above 256) for the rest."""
         n = blocks[0].norm1(t)
+        # widths the kernel has no instantiation for keep the composed route
+        fits = ops.swin_mlp_width_supported(t.shape[-1])
         for j, blk in enumerate(blocks):
             p = blk.attn(n, blk.shift, padded=True, native=True)
             t, n = ops.add_layer_norm(p, t, *_fp32_cached(blk.norm2),
                                       blk.norm2.eps)
+            n1 = blocks[j + 1].norm1 if j + 1 < len(blocks) else None
+            if blk.mlp.fused and fits:
+                ln = _fp32_cached(n1) if n1 is not None else (None, None)
+                t, n = ops.swin_mlp(n, t, *blk.mlp.prepared(), *ln,
+                                    eps=n1.eps if n1 is not None else 1e-5)
+                continue
             h = blk.mlp(n)
-            if j + 1 < len(blocks):
-                n1 = blocks[j + 1].norm1
+            if n1 is not None:
                 t, n = ops.add_layer_norm(h, t, *_fp32_cached(n1), n1.eps)
             else:
                 t = t + h

@@ -696,6 +696,148 @@ def attention_swin(
 
 
 # ---------------------------------------------------------------------------
+# the MLP half of a Swin block: fc1 + GELU + fc2 + residual (+ LayerNorm)
+# ---------------------------------------------------------------------------
+SWIN_MLP_CHUNK = 32   # hidden units the kernel walks at a time
+SWIN_MLP_MAX_C = 256
+
+
+def _swin_mlp_cpad(c: int) -> int:
+    """The kernel instantiation's column count for embed width c."""
+    return 192 if c <= 192 else 256
+
+
+def swin_mlp_width_supported(c: int) -> bool:
+    """True when swin_mlp_bf16_kernel has an instantiation for embed width c:
+    a multiple of 4 (8-byte-aligned rows), at most 256."""
+    return c % 4 == 0 and 4 <= c <= SWIN_MLP_MAX_C
+
+
+def swin_mlp_prepare(w1, b1, w2, b2):
+    """Pad an MLP's weights once for swin_mlp_bf16_kernel.
+
+    w1 [hidden, C], b1 [hidden], w2 [C, hidden], b2 [C] (nn.Linear layout) ->
+      w1p [Hp, CPAD]        w1p[j, c] = w1[j, c], zero elsewhere
+      b1p [Hp] fp32
+      w2p [Hp/32, CPAD, 32] w2p[j, c, k] = w2[c, 32 j + k], zero elsewhere
+                            (hidden chunk j as [column][hidden], the tile the
+                            kernel stages)
+      b2p [C] fp32
+    with Hp the hidden size rounded up to 32 (360 -> 384) and CPAD 192 for
+    C <= 192, else 256. The invariant: a padded hidden unit has zero w1 row
+    and zero b1, so its activation is gelu(0) = 0, and it meets zero w2
+    entries; padded columns have zero weights on both sides."""
+    hidden, c = w1.shape
+    if tuple(w2.shape) != (c, hidden) or tuple(b1.shape) != (hidden,) \
+            or tuple(b2.shape) != (c,):
+        raise ValueError(
+            f"swin_mlp_prepare: w1 {tuple(w1.shape)}, b1 {tuple(b1.shape)}, "
+            f"w2 {tuple(w2.shape)}, b2 {tuple(b2.shape)} are not fc1 "
+            "[hidden, C] / fc2 [C, hidden] with their biases")
+    if not swin_mlp_width_supported(c):
+        raise ValueError(f"swin_mlp_prepare: C = {c} must be a multiple of 4, "
+                         f"at most {SWIN_MLP_MAX_C}")
+    cpad = _swin_mlp_cpad(c)
+    hp = -(-hidden // SWIN_MLP_CHUNK) * SWIN_MLP_CHUNK
+    w1p = F.pad(w1, (0, cpad - c, 0, hp - hidden)).contiguous()
+    w2p = F.pad(w2, (0, hp - hidden, 0, cpad - c)).view(
+        cpad, hp // SWIN_MLP_CHUNK, SWIN_MLP_CHUNK).permute(1, 0, 2).contiguous()
+    b1p = F.pad(b1.float(), (0, hp - hidden)).contiguous()
+    return w1p, b1p, w2p, b2.float().contiguous()
+
+
+def _swin_mlp_kernel_reason(x, res, w1p, w2p) -> Optional[str]:
+    """Why swin_mlp_bf16_kernel does not take these, or None when it does."""
+    if not (x.is_cuda and all(t.is_cuda and t.device == x.device
+                              for t in (res, w1p, w2p))):
+        return "x, res and the weights must be on the same GPU"
+    if any(t.dtype != torch.bfloat16 for t in (x, res, w1p, w2p)):
+        return "x, res and the weights must be bf16"
+    c = x.shape[-1]
+    if not swin_mlp_width_supported(c):
+        return (f"C = {c} must be a multiple of 4, at most {SWIN_MLP_MAX_C} "
+                "(8-byte-aligned rows, one instantiation of 192 or 256 "
+                "columns)")
+    if res.shape != x.shape:
+        return f"res {tuple(res.shape)} must have x's shape {tuple(x.shape)}"
+    # rows are read in 8-byte pieces at every C; the 16-byte stores go to
+    # outputs the extension allocates
+    if not (x.is_contiguous() and res.is_contiguous()) \
+            or x.data_ptr() % 8 or res.data_ptr() % 8:
+        return "x and res must be contiguous and 8-byte aligned"
+    cpad = _swin_mlp_cpad(c)
+    if w1p.dim() != 2 or w1p.shape[1] != cpad \
+            or w1p.shape[0] % SWIN_MLP_CHUNK or w1p.shape[0] < SWIN_MLP_CHUNK \
+            or tuple(w2p.shape) != (w1p.shape[0] // SWIN_MLP_CHUNK, cpad,
+                                    SWIN_MLP_CHUNK):
+        return (f"weights must be padded by swin_mlp_prepare to w1p [Hp, "
+                f"{cpad}] and w2p [Hp/32, {cpad}, 32], got "
+                f"{tuple(w1p.shape)} and {tuple(w2p.shape)}")
+    if not (w1p.is_contiguous() and w2p.is_contiguous()) \
+            or w1p.data_ptr() % 16 or w2p.data_ptr() % 16:
+        return "padded weights must be contiguous and 16-byte aligned"
+    return None
+
+
+def _swin_mlp_vector_reason(x, w1p, b1p, b2, ln_weight,
+                            ln_bias) -> Optional[str]:
+    """Why swin_mlp_bf16_kernel does not take one of its fp32 vectors (b1p
+    [Hp], the rest [C]; the norm's pair may be None), or None when it does."""
+    c = x.shape[-1]
+    vectors = [("b1", b1p, w1p.shape[0]), ("b2", b2, c)]
+    if ln_weight is not None:
+        vectors += [("ln_weight", ln_weight, c), ("ln_bias", ln_bias, c)]
+    for name, t, n in vectors:
+        if not (t.is_cuda and t.device == x.device):
+            return f"{name} must be on x's GPU"
+        if t.dtype != torch.float32:
+            return f"{name} must be fp32, got {t.dtype}"
+        if tuple(t.shape) != (n,):
+            return f"{name} must be [{n}], got {tuple(t.shape)}"
+        if not t.is_contiguous() or t.data_ptr() % 16:
+            return f"{name} must be contiguous and 16-byte aligned"
+    return None
+
+
+def swin_mlp_supported(x, res, w1p, w2p) -> bool:
+    """True when swin_mlp runs swin_mlp_bf16_kernel on these: contiguous,
+    8-byte-aligned bf16 x and res of one shape on the GPU, C % 4 == 0,
+    C <= 256, weights as swin_mlp_prepare leaves them."""
+    return _swin_mlp_kernel_reason(x, res, w1p, w2p) is None
+
+
+def swin_mlp(x, res, w1, b1, w2, b2, ln_weight=None, ln_bias=None,
+             eps: float = 1e-5, native: bool = True):
+    """(s, LayerNorm(s)) with s = res + fc2(gelu(fc1(x))), the MLP half of a
+    Swin block and the norm that follows it, over [..., C] token rows. The
+    second result is None when no norm weights are given.
+
+    bf16 x on the GPU with native=True runs swin_mlp_bf16_kernel
+    (ops/hip/swin_mlp.hip) and takes the weights as swin_mlp_prepare leaves
+    them (b1, b2 and the norm's tensors fp32): the hidden activation stays in
+    registers, rounded to bf16 once, and the norm is taken from the fp32 sum.
+    What the kernel does not take raises ValueError with the reason; nothing
+    is composed silently. CPU tensors, other dtypes and native=False take the
+    literal torch route on UNPADDED nn.Linear weights."""
+    if (ln_weight is None) != (ln_bias is None):
+        raise ValueError("swin_mlp: give both ln_weight and ln_bias or neither")
+    if native and x.is_cuda and x.dtype == torch.bfloat16:
+        why = _swin_mlp_kernel_reason(x, res, w1, w2) \
+            or _swin_mlp_vector_reason(x, w1, b1, b2, ln_weight, ln_bias)
+        if why is not None:
+            raise ValueError(f"swin_mlp: {why}")
+        c = x.shape[-1]
+        out = ext().swin_mlp(x.view(-1, c), res.view(-1, c), w1, b1, w2, b2,
+                             ln_weight, ln_bias, eps)
+        return out[0].view(x.shape), \
+            (out[1].view(x.shape) if len(out) > 1 else None)
+    s = res + F.linear(F.gelu(F.linear(x, w1, b1)), w2, b2)
+    if ln_weight is None:
+        return s, None
+    return s, F.layer_norm(s, (s.shape[-1],), ln_weight, ln_bias, eps)
+
+
+# ---------------------------------------------------------------------------
 # Hypertile: self-attention inside rectangular windows of the token grid
 # ---------------------------------------------------------------------------
 def _window_extent(n: int, least: int) -> int:

@@ -17,6 +17,7 @@ static inline hipStream_t cur_stream() {
 #include "attention.hip"
 #include "attention_wide.hip"
 #include "attention_swin.hip"
+#include "swin_mlp.hip"
 #include "conv_v4.hip"
 #include "conv.hip"
 #include "conv_small.hip"
@@ -729,6 +730,77 @@ torch::Tensor attention_swin(torch::Tensor qkv, torch::Tensor bias,
   return swin_attn_raw(qkv, bias, scale, shift);
 }
 
+std::vector<torch::Tensor> swin_mlp(torch::Tensor x, torch::Tensor res,
+                                    torch::Tensor w1p, torch::Tensor b1p,
+                                    torch::Tensor w2p, torch::Tensor b2,
+                                    c10::optional<torch::Tensor> ln_w,
+                                    c10::optional<torch::Tensor> ln_b,
+                                    double eps) {
+  // x, res [R, C] bf16; w1p [Hp, CPAD], w2p [Hp/32, CPAD, 32] bf16 and b1p
+  // [Hp], b2 [C] fp32 as ops.swin_mlp_prepare leaves them
+  // (swin_mlp_bf16_kernel). Returns {sum} or {sum, ln}. Everything an address
+  // is formed from is checked here; rows are addressed with 64-bit offsets.
+  // x and res are read in 8-byte pieces at every C (the 16-byte stores go to
+  // the outputs allocated below); the weights are staged in 16-byte pieces
+  auto bf16_gpu = [&](const torch::Tensor &t, int align) {
+    return t.is_cuda() && t.get_device() == x.get_device() &&
+           t.scalar_type() == torch::kBFloat16 && t.is_contiguous() &&
+           ((uintptr_t)t.data_ptr()) % align == 0;
+  };
+  auto f32_gpu = [&](const torch::Tensor &t, long n) {
+    return t.is_cuda() && t.get_device() == x.get_device() &&
+           t.scalar_type() == torch::kFloat32 && t.dim() == 1 &&
+           t.size(0) == n && t.is_contiguous() &&
+           ((uintptr_t)t.data_ptr()) % 16 == 0;
+  };
+  TORCH_CHECK(x.dim() == 2 && bf16_gpu(x, 8),
+              "swin_mlp: x must be a contiguous, 8-byte-aligned bf16 [R, C] "
+              "on the GPU");
+  TORCH_CHECK(res.sizes() == x.sizes() && bf16_gpu(res, 8),
+              "swin_mlp: res must be a contiguous, 8-byte-aligned bf16 tensor "
+              "of x's shape on x's GPU");
+  const long R = x.size(0), C = x.size(1);
+  TORCH_CHECK(C >= 4 && C % 4 == 0 && C <= 256,
+              "swin_mlp: C = ", C, " must be a multiple of 4, at most 256");
+  const long cpad = C <= 192 ? 192 : 256;
+  TORCH_CHECK(w1p.dim() == 2 && w1p.size(1) == cpad && w1p.size(0) >= MLP_HC &&
+                  w1p.size(0) % MLP_HC == 0 && bf16_gpu(w1p, 16),
+              "swin_mlp: w1p must be a contiguous, 16-byte-aligned bf16 "
+              "[Hp, ", cpad, "] with Hp a multiple of 32 (swin_mlp_prepare)");
+  const long hp = w1p.size(0);
+  TORCH_CHECK(w2p.dim() == 3 && w2p.size(0) == hp / MLP_HC &&
+                  w2p.size(1) == cpad && w2p.size(2) == MLP_HC &&
+                  bf16_gpu(w2p, 16),
+              "swin_mlp: w2p must be a contiguous, 16-byte-aligned bf16 "
+              "[Hp/32, ", cpad, ", 32] (swin_mlp_prepare)");
+  TORCH_CHECK(f32_gpu(b1p, hp) && f32_gpu(b2, C),
+              "swin_mlp: b1p must be fp32 [Hp] and b2 fp32 [C], contiguous "
+              "and 16-byte aligned");
+  TORCH_CHECK(ln_w.has_value() == ln_b.has_value(),
+              "swin_mlp: give both LayerNorm tensors or neither");
+  const float *gamma = nullptr, *beta = nullptr;
+  if (ln_w.has_value()) {
+    TORCH_CHECK(f32_gpu(*ln_w, C) && f32_gpu(*ln_b, C),
+                "swin_mlp: the LayerNorm weight and bias must be fp32 [C], "
+                "contiguous and 16-byte aligned");
+    gamma = (const float *)ln_w->data_ptr();
+    beta = (const float *)ln_b->data_ptr();
+  }
+  TORCH_CHECK((R + MLP_ROWS - 1) / MLP_ROWS < (1L << 31),
+              "swin_mlp: too many rows");
+  std::vector<torch::Tensor> out{torch::empty_like(x)};
+  if (gamma) out.push_back(torch::empty_like(x));
+  if (R == 0) return out;
+  void *ln = gamma ? out[1].data_ptr() : nullptr;
+  if (cpad == 192)
+    swin_mlp_launch<192>(x, res, w1p, b1p, w2p, b2, gamma, beta, out[0], ln,
+                         eps);
+  else
+    swin_mlp_launch<256>(x, res, w1p, b1p, w2p, b2, gamma, beta, out[0], ln,
+                         eps);
+  return out;
+}
+
 torch::Tensor attention_blend_bshd(torch::Tensor q, torch::Tensor k,
                                    torch::Tensor v, torch::Tensor w,
                                    torch::Tensor kv_index,
@@ -933,6 +1005,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_swin", &attention_swin, py::arg("qkv"), py::arg("bias"),
         py::arg("scale"), py::arg("shift"));
   m.def("attention_swin_plan", &attention_swin_plan);
+  m.def("swin_mlp", &swin_mlp, py::arg("x"), py::arg("res"), py::arg("w1p"),
+        py::arg("b1p"), py::arg("w2p"), py::arg("b2"),
+        py::arg("ln_w") = py::none(), py::arg("ln_b") = py::none(),
+        py::arg("eps") = 1e-5);
   m.def("probe_mfma32", &probe_mfma32);
   m.def("probe_mfma16", &probe_mfma16);
   m.def("probe_tr16", &probe_tr16);

@@ -11,6 +11,12 @@ the bias once; the two routes' outputs are compared at every timed size
 before timing. Then SwinIR-L (embed 240, 9 x 6 blocks, 3conv) on a
 --image x --image input. Each figure is the median of --rounds alternating
 rounds. One JSON object on stdout.
+
+--mlp runs the MLP section instead: per grid, ops.swin_mlp
+(swin_mlp_bf16_kernel) against F.linear, F.gelu, F.linear, ops.add_layer_norm
+at (C, hidden) = (180, 360) and (240, 480), with per-call time and the
+compulsory bytes of either route, then SwinIR-M and SwinIR-L with Mlp.fused on
+against off.
 """
 import argparse
 import json
@@ -20,6 +26,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+import torch.nn.functional as F
 from sdwd_amd import ops
 from sdwd_amd.models.swinir import SwinIR
 
@@ -34,6 +41,10 @@ ap.add_argument("--model-iters", type=int, default=2)
 ap.add_argument("--limit", type=float, default=20.0,
                 help="seconds a single timing step may take")
 ap.add_argument("--skip-model", action="store_true")
+ap.add_argument("--mlp", action="store_true",
+                help="instead: ops.swin_mlp against the composed route per "
+                     "grid at (180, 360) and (240, 480), then SwinIR-M and "
+                     "SwinIR-L with Mlp.fused on against off")
 args = ap.parse_args()
 assert torch.cuda.is_available(), "swinir_perf needs a GPU"
 DEV = "cuda"
@@ -122,6 +133,103 @@ def model_row(size):
             "speedup": round(r["plain"]["med"] / r["native"]["med"], 3),
             "max_abs_diff_native_plain": diff, "max_abs_plain": amp}
 
+
+def mlp_row(grid, c, hidden):
+    """One block's MLP half with the next norm: ops.swin_mlp against
+    F.linear, F.gelu, F.linear, ops.add_layer_norm on the same tensors."""
+    g = torch.Generator(device=DEV).manual_seed(grid + c)
+
+    def n(*s, dt=torch.bfloat16):
+        return torch.randn(*s, device=DEV, generator=g).to(dt)
+
+    shape = (args.batch, grid, grid, c)
+    x, res = n(*shape), 2 * n(*shape)
+    w1, b1 = n(hidden, c) / c ** 0.5, 0.5 * n(hidden)
+    w2, b2 = n(c, hidden) / hidden ** 0.5, 0.5 * n(c)
+    gm, bt = 1 + 0.5 * n(c, dt=torch.float32), 0.5 * n(c, dt=torch.float32)
+    prep = ops.swin_mlp_prepare(w1, b1, w2, b2)
+
+    def fused():
+        return ops.swin_mlp(x, res, *prep, gm, bt)
+
+    def composed():
+        h = F.linear(F.gelu(F.linear(x, w1, b1)), w2, b2)
+        return ops.add_layer_norm(h, res, gm, bt)
+
+    # both routes round the sum to bf16 once (the composed one h and fc2's
+    # output as well): they agree within a few bf16 steps of the largest sum
+    (s0, l0), (s1, l1) = fused(), composed()
+    diff = max((s0.float() - s1.float()).abs().max().item(),
+               (l0.float() - l1.float()).abs().max().item())
+    amp = s1.float().abs().max().item()
+    assert diff <= 2.0 ** -6 * amp, (grid, c, diff, amp)
+    r = alternate({"fused": fused, "composed": composed}, args.iters)
+    rows = x.numel() // c
+    nbytes = 4 * rows * c * 2                      # x, res in; sum, ln out
+    comp = 14 * rows * c * 2                       # the four passes, hidden 2C
+    cpad, hp = prep[0].shape[1], prep[0].shape[0]
+    us = {k: [round(v[s] * 1e6, 2) for s in ("med", "min", "max")]
+          for k, v in r.items()}
+    return {
+        "fused_us_med_min_max": us["fused"],
+        "composed_us_med_min_max": us["composed"],
+        "fused_compulsory_bytes": nbytes,
+        "composed_compulsory_bytes": comp,
+        "fused_gb_s": round(nbytes / r["fused"]["med"] / 1e9, 1),
+        "composed_gb_s": round(comp / r["composed"]["med"] / 1e9, 1),
+        "flop": 4 * rows * c * hidden,
+        "padded_flop": 4 * rows * cpad * hp,
+        "speedup": round(r["composed"]["med"] / r["fused"]["med"], 3),
+        "fused_below_composed_min": r["fused"]["med"] < r["composed"]["min"],
+        "max_abs_diff_fused_composed": diff,
+    }
+
+
+def mlp_model_row(size, *cfg):
+    """The whole model with Mlp.fused on against off, alternating."""
+    from sdwd_amd.models.swinir import Mlp
+
+    torch.manual_seed(0)
+    net = SwinIR(*cfg).eval().to(DEV, torch.bfloat16)
+    x = torch.rand(1, 3, size, size, device=DEV, dtype=torch.bfloat16)
+
+    def run(flag):
+        def fn():
+            Mlp.fused = flag
+            return net(x)
+        return fn
+
+    default = Mlp.fused
+    with torch.no_grad():
+        a, b = run(True)().float(), run(False)().float()
+        diff, amp = (a - b).abs().max().item(), b.abs().max().item()
+        del a, b
+        r = alternate({"fused": run(True), "composed": run(False)},
+                      args.model_iters)
+    Mlp.fused = default
+    ms = {k: [round(v[s] * 1e3, 2) for s in ("med", "min", "max")]
+          for k, v in r.items()}
+    return {"fused_ms_med_min_max": ms["fused"],
+            "composed_ms_med_min_max": ms["composed"],
+            "speedup": round(r["composed"]["med"] / r["fused"]["med"], 3),
+            "fused_below_composed_min": r["fused"]["med"] < r["composed"]["min"],
+            "max_abs_diff_fused_composed": diff, "max_abs_composed": amp}
+
+
+if args.mlp:
+    out = {"mlp": {}}
+    for grid in args.grids:
+        for c, hidden in ((180, 360), (240, 480)):
+            out["mlp"][f"{grid}x{grid} C={c} hidden={hidden} B={args.batch}"] = \
+                mlp_row(grid, c, hidden)
+    if not args.skip_model:
+        size = args.image
+        out[f"SwinIR-M {size}x{size}"] = mlp_model_row(
+            size, 180, (6,) * 6, 6, 2.0, "1conv")
+        out[f"SwinIR-L {size}x{size}"] = mlp_model_row(
+            size, 240, (6,) * 9, 8, 2.0, "3conv")
+    print(json.dumps(out, indent=1))
+    sys.exit(0)
 
 out = {"attention": {}}
 for grid in args.grids:
