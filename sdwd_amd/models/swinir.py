@@ -11,14 +11,16 @@ On a bf16 GPU the tokens stay one [B, H, W, C] tensor from conv_first to the
 tail. A Swin block is: ops.layer_norm, the QKV GEMM, ops.attention_swin on the
 GEMM's output viewed as [B, H, W, 3, heads, 32], the proj GEMM,
 ops.add_layer_norm (residual + norm2), and ops.swin_mlp: fc1, GELU, fc2, the
-residual and the next block's norm1 in one kernel (Mlp.fused). Nothing is
+residual and the next block's norm1 in one kernel (Mlp.fused). The convs at
+the embed width (an RSTB's closing conv or 3conv stack, conv_after_body,
+conv_before_upsample) run on ops.conv_ragged with their LeakyReLU and their
+residual in the epilogue (SwinIR.native_convs). Nothing is
 rolled, partitioned, masked or permuted. Each head's 30 q/k/v rows are
 zero-padded to 32 once per weight version so a head row is 64 bytes: padded
 q/k channels add 0 to every score and padded v channels meet zero proj
 columns; the MLP's weights are zero-padded once the same way
-(ops.swin_mlp_prepare). The QKV and proj GEMMs and the 3x3 convs at 180 / 240
-channels (Cin % 64 != 0, one per six attention blocks) stay on the library,
-and so does the MLP at an embed width the kernel has no instantiation for
+(ops.swin_mlp_prepare), and so are the conv weights (ops.conv_ragged_prepare).
+The QKV and proj GEMMs stay on the library, and so does the MLP at an embed width the kernel has no instantiation for
 (no multiple of 4, or above 256), which runs composed as with Mlp.fused off.
 """
 from __future__ import annotations
@@ -205,9 +207,27 @@ def _tokens(img: torch.Tensor) -> torch.Tensor:
     return img.permute(0, 2, 3, 1)
 
 
+def _ragged_prepared(conv: SDConv2d) -> torch.Tensor:
+    """ops.conv_ragged_prepare of the conv's weight, rebuilt when the weight
+    changes (like SDConv2d._wprep)."""
+    w = conv.weight
+    key = (w.data_ptr(), w._version, w.dtype)
+    cache = getattr(conv, "_ragged_cache", None)
+    if cache is None or cache[0] != key:
+        with torch.no_grad():
+            cache = (key, ops.conv_ragged_prepare(w))
+        conv._ragged_cache = cache
+    return cache[1]
+
+
 class SwinIR(nn.Module):
     """SwinIR(embed_dim, depths, heads, mlp_ratio, resi_connection), 4x
     nearest+conv: [N, 3, H, W] in 0..1 -> [N, 3, 4H, 4W]."""
+
+    # the native route runs the convs at the embed width (and their 3conv
+    # stacks) on ops.conv_ragged with the activation and the residual in the
+    # epilogue; False keeps the library conv plus elementwise passes
+    native_convs = True
 
     def __init__(self, embed_dim: int = 180, depths=(6,) * 6,
                  num_heads: int = 6, mlp_ratio: float = 2.0,
@@ -306,6 +326,47 @@ class SwinIR(nn.Module):
                 t = t + h
         return t
 
+    def _conv_native(self, m: nn.Module, x: torch.Tensor, res=None):
+        """act(conv(x)) + res for a conv, or a Sequential of convs and
+        LeakyReLUs, on ops.conv_ragged: one launch per conv, its LeakyReLU
+        and (on the last one) the residual in the epilogue. x and res are
+        NHWC views [N, C, H, W]. None when native_convs is off or a conv is
+        outside the kernel's range: the caller keeps the library route."""
+        if not self.native_convs:
+            return None
+        mods = list(m) if isinstance(m, nn.Sequential) else [m]
+        steps = []          # (conv, slope of the LeakyReLU behind it or None)
+        for sub in mods:
+            if isinstance(sub, nn.LeakyReLU) and steps and steps[-1][1] is None:
+                steps[-1] = (steps[-1][0], sub.negative_slope)
+            elif isinstance(sub, SDConv2d):
+                steps.append((sub, None))
+            else:
+                return None
+        if steps[-1][1] is not None and res is not None:
+            return None     # the epilogue activates before the residual only
+        n, _, h, w = x.shape
+        outs = []
+        for conv, _ in steps:
+            k = conv.kernel_size
+            out = torch.empty((n, conv.out_channels, h, w), dtype=x.dtype,
+                              device=x.device,
+                              memory_format=torch.channels_last)
+            if (k[0] != k[1] or conv.padding != (k[0] // 2, k[0] // 2)
+                    or conv.stride != (1, 1) or conv.dilation != (1, 1)
+                    or conv.groups != 1
+                    or getattr(conv, "circular", False)
+                    or not ops.conv_ragged_supported(
+                        outs[-1] if outs else x, conv.weight, out)):
+                return None
+            outs.append(out)
+        for i, ((conv, slope), out) in enumerate(zip(steps, outs)):
+            x = ops.conv_ragged(
+                x, _ragged_prepared(conv), conv.bias, out,
+                ksize=conv.kernel_size[0], lrelu=slope,
+                res=res if i + 1 == len(steps) else None)
+        return x
+
     def _forward_native(self, x: torch.Tensor) -> torch.Tensor:
         x = x.contiguous(memory_format=torch.channels_last)
         first = self.conv_first(x).contiguous(
@@ -313,9 +374,18 @@ class SwinIR(nn.Module):
         t = self.patch_embed.norm(_tokens(first))
         for layer in self.layers:
             body = self._blocks_native(t, list(layer.residual_group.blocks))
-            t = _tokens(layer.conv(_nchw(body))).contiguous() + t
-        feat = self.conv_after_body(_nchw(self.norm(t))) + first
-        feat = self.conv_before_upsample(feat)
+            y = self._conv_native(layer.conv, _nchw(body), res=_nchw(t))
+            if y is not None:
+                t = _tokens(y)
+            else:
+                t = _tokens(layer.conv(_nchw(body))).contiguous() + t
+        body = _nchw(self.norm(t))
+        feat = self._conv_native(self.conv_after_body, body, res=first)
+        if feat is None:
+            feat = self.conv_after_body(body) + first
+        body, feat = feat, self._conv_native(self.conv_before_upsample, feat)
+        if feat is None:
+            feat = self.conv_before_upsample(body)
         for up in (self.conv_up1, self.conv_up2):
             feat = F.leaky_relu_(up.forward_upsampled2x(feat), SLOPE)  # FOLD
         feat = feat.contiguous(memory_format=torch.channels_last)

@@ -1745,6 +1745,163 @@ def conv3x3_dense(
 
 
 # ---------------------------------------------------------------------------
+# 3x3 / 1x1 conv at channel widths that are no multiple of 64 (SwinIR's convs
+# at embed 180 / 240 and their 60-wide stacks, models/swinir.py)
+# ---------------------------------------------------------------------------
+def _ragged_padded(cin: int, cout: int) -> Tuple[int, int]:
+    """(ceil32(Cin), ceil64(Cout)): the prepared weight's padded widths."""
+    return -(-cin // 32) * 32, -(-cout // 64) * 64
+
+
+def conv_ragged_prepare(weight: torch.Tensor) -> torch.Tensor:
+    """A conv weight [Cout, Cin, KS, KS] (KS 1 or 3) as conv_ragged reads it:
+    [ceil64(Cout), KS, KS, ceil32(Cin)] in the weight's dtype, exact zeros
+    outside the real block, so the kernel stages whole 16-byte pieces of
+    whole 64-row tiles without masks. Callers cache it per weight version."""
+    if (not torch.is_tensor(weight) or weight.dim() != 4
+            or weight.shape[2] != weight.shape[3]
+            or weight.shape[2] not in (1, 3)):
+        raise ValueError("conv_ragged_prepare: weight must be "
+                         "[Cout, Cin, KS, KS] with KS 1 or 3")
+    cout, cin, ks, _ = weight.shape
+    cinp, coutp = _ragged_padded(cin, cout)
+    prep = weight.new_zeros(coutp, ks, ks, cinp)
+    prep[:cout, :, :, :cin] = weight.detach().permute(0, 2, 3, 1)
+    return prep
+
+
+def _ragged_nhwc(t: torch.Tensor) -> bool:
+    """A channel slice of an NHWC buffer the ragged kernel can address: unit
+    channel stride, rows of W pixels, pixel and image strides that are
+    multiples of 4 elements, an 8-byte-aligned base, offsets below 2^31."""
+    n, c, h, w = t.shape
+    ld = t.stride(3)
+    return bool(
+        t.stride(1) == 1 and ld >= c and ld % 4 == 0
+        and t.stride(2) == w * ld
+        and (n == 1 or (t.stride(0) % 4 == 0 and t.stride(0) >= h * w * ld))
+        and t.data_ptr() % 8 == 0 and h * w * ld < 2 ** 31
+    )
+
+
+def conv_ragged_supported(x, weight, out) -> bool:
+    """True when conv_ragged runs conv_ragged_bf16_kernel for the conv weight
+    [Cout, Cin, KS, KS] on these views: bf16 on the GPU, KS 1 or 3, Cin and
+    Cout multiples of 4 in [4, 512], N <= 65535, NHWC channel slices (unit
+    channel stride, pixel strides % 4 == 0, 8-byte-aligned bases). The
+    routing predicate."""
+    return bool(
+        x.is_cuda and out.is_cuda and weight.is_cuda
+        and x.dtype == out.dtype == weight.dtype == torch.bfloat16
+        and x.dim() == out.dim() == weight.dim() == 4
+        and weight.shape[2] == weight.shape[3]
+        and tuple(weight.shape[:2]) == (out.shape[1], x.shape[1])
+        and ext().conv_ragged_supported_widths(
+            x.shape[1], out.shape[1], weight.shape[2])
+        and 1 <= x.shape[0] <= 65535 and x.shape[2] >= 1 and x.shape[3] >= 1
+        and tuple(out.shape) == (x.shape[0], out.shape[1]) + tuple(x.shape[2:])
+        and _ragged_nhwc(x) and _ragged_nhwc(out)
+    )
+
+
+def conv_ragged(
+    x: torch.Tensor,
+    w_prepared: torch.Tensor,
+    bias: Optional[torch.Tensor],
+    out: torch.Tensor,
+    ksize: int = 3,
+    lrelu: Optional[float] = None,
+    res: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """out <- act(conv(x, w) + bias) + res: a stride-1 "same" conv with a
+    ksize x ksize kernel (3 or 1); act is LeakyReLU(lrelu) when lrelu is
+    given. Written in place into `out`, which is returned.
+
+    x, out, res are [N, C, H, W] views with unit channel stride (channel
+    slices of channels_last buffers). out must not share channels with x;
+    res is disjoint from out or exactly out's slice. w_prepared is
+    conv_ragged_prepare(weight) for x's Cin and out's Cout.
+
+    bf16 on the GPU with Cin and Cout multiples of 4 in [4, 512] and views
+    the kernel can address: conv_ragged_bf16_kernel (ops/hip/conv_ragged.hip),
+    fp32 accumulate, one bf16 rounding. CPU, or otherwise: the same formula
+    with F.conv2d (fp32 math for bf16) on the unpadded block of w_prepared,
+    copied into out. A bad argument raises ValueError naming it.
+    """
+    name = "conv_ragged"
+    for nm, t in (("x", x), ("w_prepared", w_prepared), ("out", out)):
+        if not torch.is_tensor(t) or t.dim() != 4:
+            raise ValueError(f"{name}: {nm} must be a 4-d tensor")
+    if ksize not in (1, 3):
+        raise ValueError(f"{name}: ksize must be 1 or 3, got {ksize!r}")
+    n, cin, h, w = x.shape
+    cout = out.shape[1]
+    if min(n, cin, h, w) < 1:
+        raise ValueError(f"{name}: x must be non-empty, got {tuple(x.shape)}")
+    cinp, coutp = _ragged_padded(cin, cout)
+    if tuple(w_prepared.shape) != (coutp, ksize, ksize, cinp):
+        raise ValueError(
+            f"{name}: w_prepared must be [ceil64(Cout),KS,KS,ceil32(Cin)] = "
+            f"{(coutp, ksize, ksize, cinp)}, got {tuple(w_prepared.shape)}"
+        )
+    if bias is not None and bias.numel() != cout:
+        raise ValueError(f"{name}: bias must hold {cout} values, got "
+                         f"{bias.numel()}")
+    views = [("out", out), ("res", res)]
+    for nm, t in views:
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or tuple(t.shape) != (n, cout, h, w):
+            raise ValueError(
+                f"{name}: {nm} must be {(n, cout, h, w)}, got "
+                f"{tuple(t.shape) if torch.is_tensor(t) else type(t)}"
+            )
+    for nm, t in (("w_prepared", w_prepared), ("bias", bias)) + tuple(views):
+        if t is None:
+            continue
+        if t.device != x.device:
+            raise ValueError(f"{name}: {nm} is on {t.device}, x on {x.device}")
+        if nm != "bias" and t.dtype != x.dtype:
+            raise ValueError(f"{name}: {nm} is {t.dtype}, x is {x.dtype}")
+    for nm, t in (("x", x),) + tuple(views):
+        if t is not None and t.stride(1) != 1:
+            raise ValueError(f"{name}: {nm} needs unit channel stride "
+                             "(a channel slice of a channels_last buffer)")
+    if _dense_overlap(out, x) != "disjoint":
+        raise ValueError(f"{name}: out shares channels with x")
+    if res is not None and _dense_overlap(out, res) == "overlap":
+        raise ValueError(f"{name}: out partly overlaps res; the residual is "
+                         "disjoint from out or exactly its slice")
+    if lrelu is not None and not isinstance(lrelu, (int, float)):
+        raise ValueError(f"{name}: lrelu must be a slope or None")
+
+    native = bool(
+        x.is_cuda and x.dtype == torch.bfloat16
+        and ext().conv_ragged_supported_widths(cin, cout, ksize)
+        and n <= 65535 and w_prepared.is_contiguous()
+        and w_prepared.data_ptr() % 16 == 0
+        and all(t is None or _ragged_nhwc(t) for t in (x, out, res))
+    )
+    if native:
+        return ext().conv_ragged(
+            x, w_prepared, bias, out, int(ksize), res, lrelu is not None,
+            float(lrelu or 0.0),
+        )
+    wide = x.dtype == torch.bfloat16
+    up = (lambda t: t.float()) if wide else (lambda t: t)
+    y = F.conv2d(
+        up(x), up(w_prepared[:cout, :, :, :cin]).permute(0, 3, 1, 2),
+        None if bias is None else bias.to(up(x).dtype), padding=ksize // 2,
+    )
+    if lrelu is not None:
+        y = F.leaky_relu(y, float(lrelu))
+    if res is not None:
+        y = y + up(res)
+    out.copy_(y)
+    return out
+
+
+# ---------------------------------------------------------------------------
 # timestep embedding (sinusoidal)
 # ---------------------------------------------------------------------------
 def timestep_embedding(

@@ -22,6 +22,7 @@ static inline hipStream_t cur_stream() {
 #include "conv.hip"
 #include "conv_small.hip"
 #include "conv_dense.hip"
+#include "conv_ragged.hip"
 #include "rng.hip"
 #include "tome.hip"
 
@@ -1033,4 +1034,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias"), py::arg("out"), py::arg("alpha"), py::arg("res1"),
         py::arg("beta"), py::arg("res2"), py::arg("lrelu"), py::arg("slope"));
   m.def("conv3x3_dense_supported_widths", &conv3x3_dense_supported_widths);
+  m.def("conv_ragged", &conv_ragged, py::arg("x"), py::arg("w_prep"),
+        py::arg("bias"), py::arg("out"), py::arg("ksize"), py::arg("res"),
+        py::arg("lrelu"), py::arg("slope"));
+  m.def("conv_ragged_supported_widths", &conv_ragged_supported_widths);
 }

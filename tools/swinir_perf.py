@@ -17,6 +17,13 @@ rounds. One JSON object on stdout.
 at (C, hidden) = (180, 360) and (240, 480), with per-call time and the
 compulsory bytes of either route, then SwinIR-M and SwinIR-L with Mlp.fused on
 against off.
+
+--conv runs the conv section instead: per grid, ops.conv_ragged
+(conv_ragged_bf16_kernel) against the route it replaces, SDConv2d on the
+library plus the add or LeakyReLU pass that conv needs, at 180 -> 180 with a
+residual, 240 -> 60 with LeakyReLU, 60 -> 60 1x1 with LeakyReLU, 60 -> 240 with
+a residual and 240 -> 64 with LeakyReLU; then SwinIR-M and SwinIR-L with
+SwinIR.native_convs on against off.
 """
 import argparse
 import json
@@ -45,6 +52,10 @@ ap.add_argument("--mlp", action="store_true",
                 help="instead: ops.swin_mlp against the composed route per "
                      "grid at (180, 360) and (240, 480), then SwinIR-M and "
                      "SwinIR-L with Mlp.fused on against off")
+ap.add_argument("--conv", action="store_true",
+                help="instead: ops.conv_ragged against the library conv plus "
+                     "its elementwise pass per grid and shape, then SwinIR-M "
+                     "and SwinIR-L with SwinIR.native_convs on against off")
 args = ap.parse_args()
 assert torch.cuda.is_available(), "swinir_perf needs a GPU"
 DEV = "cuda"
@@ -215,6 +226,111 @@ def mlp_model_row(size, *cfg):
             "fused_below_composed_min": r["fused"]["med"] < r["composed"]["min"],
             "max_abs_diff_fused_composed": diff, "max_abs_composed": amp}
 
+
+# (Cin, Cout, ksize, LeakyReLU slope or None, residual)
+CONV_SHAPES = [(180, 180, 3, None, True), (240, 60, 3, 0.2, False),
+               (60, 60, 1, 0.2, False), (60, 240, 3, None, True),
+               (240, 64, 3, 0.01, False)]
+
+
+def conv_row(grid, cin, cout, ks, slope, with_res):
+    """One conv with its epilogue: ops.conv_ragged against SDConv2d on the
+    library, then what SwinIR's route without the kernel does to its output
+    (.contiguous() + t on the tokens, or the LeakyReLU module)."""
+    from sdwd_amd.models.layers import SDConv2d
+
+    torch.manual_seed(grid + cin + cout)
+    conv = SDConv2d(cin, cout, ks, padding=ks // 2).to(DEV, torch.bfloat16)
+    act = torch.nn.LeakyReLU(slope) if slope is not None else None
+    b = args.batch
+    t_in = torch.randn(b, grid, grid, cin, device=DEV, dtype=torch.bfloat16)
+    t_res = (torch.randn(b, grid, grid, cout, device=DEV,
+                         dtype=torch.bfloat16) if with_res else None)
+    x = t_in.permute(0, 3, 1, 2)
+    out = torch.empty(b, cout, grid, grid, device=DEV, dtype=torch.bfloat16,
+                      memory_format=torch.channels_last)
+    assert ops.conv_ragged_supported(x, conv.weight, out)
+    wp = ops.conv_ragged_prepare(conv.weight)
+    res = None if t_res is None else t_res.permute(0, 3, 1, 2)
+
+    def native():
+        return ops.conv_ragged(x, wp, conv.bias, out, ksize=ks, lrelu=slope,
+                               res=res)
+
+    def composed():
+        y = conv(x)
+        if act is not None:
+            y = act(y)
+        if t_res is not None:
+            return (y.permute(0, 2, 3, 1).contiguous() + t_res
+                    ).permute(0, 3, 1, 2)
+        return y
+
+    with torch.no_grad():
+        # the kernel rounds once, the composed route after the conv and again
+        # after the pass: a few bf16 steps of the largest output
+        y0, y1 = native().float(), composed().float()
+        diff, amp = (y0 - y1).abs().max().item(), y1.abs().max().item()
+        assert diff <= 2.0 ** -6 * amp, (grid, cin, cout, diff, amp)
+        del y0, y1
+        r = alternate({"native": native, "composed": composed}, args.iters)
+    flop = 2 * b * grid * grid * cin * cout * ks * ks
+    us = {k: [round(v[s] * 1e6, 2) for s in ("med", "min", "max")]
+          for k, v in r.items()}
+    return {
+        "native_us_med_min_max": us["native"],
+        "composed_us_med_min_max": us["composed"],
+        "flop": flop,
+        "native_tflop_s": round(flop / r["native"]["med"] / 1e12, 1),
+        "composed_tflop_s": round(flop / r["composed"]["med"] / 1e12, 1),
+        "speedup": round(r["composed"]["med"] / r["native"]["med"], 3),
+        "native_below_composed_min": r["native"]["med"] < r["composed"]["min"],
+        "max_abs_diff_native_composed": diff,
+    }
+
+
+def conv_model_row(size, *cfg):
+    """The whole model with SwinIR.native_convs on against off, alternating."""
+    torch.manual_seed(0)
+    net = SwinIR(*cfg).eval().to(DEV, torch.bfloat16)
+    x = torch.rand(1, 3, size, size, device=DEV, dtype=torch.bfloat16)
+
+    def run(flag):
+        def fn():
+            net.native_convs = flag
+            return net(x)
+        return fn
+
+    with torch.no_grad():
+        a, b = run(True)().float(), run(False)().float()
+        diff, amp = (a - b).abs().max().item(), b.abs().max().item()
+        del a, b
+        r = alternate({"native": run(True), "library": run(False)},
+                      args.model_iters)
+    ms = {k: [round(v[s] * 1e3, 2) for s in ("med", "min", "max")]
+          for k, v in r.items()}
+    return {"native_convs_ms_med_min_max": ms["native"],
+            "library_convs_ms_med_min_max": ms["library"],
+            "speedup": round(r["library"]["med"] / r["native"]["med"], 3),
+            "native_below_library_min": r["native"]["med"] < r["library"]["min"],
+            "max_abs_diff_native_library": diff, "max_abs_library": amp}
+
+
+if args.conv:
+    out = {"conv": {}}
+    for grid in args.grids:
+        for cin, cout, ks, slope, with_res in CONV_SHAPES:
+            key = (f"{grid}x{grid} {cin}->{cout} ks={ks} lrelu={slope} "
+                   f"res={with_res} B={args.batch}")
+            out["conv"][key] = conv_row(grid, cin, cout, ks, slope, with_res)
+    if not args.skip_model:
+        size = args.image
+        out[f"SwinIR-M {size}x{size}"] = conv_model_row(
+            size, 180, (6,) * 6, 6, 2.0, "1conv")
+        out[f"SwinIR-L {size}x{size}"] = conv_model_row(
+            size, 240, (6,) * 9, 8, 2.0, "3conv")
+    print(json.dumps(out, indent=1))
+    sys.exit(0)
 
 if args.mlp:
     out = {"mlp": {}}
