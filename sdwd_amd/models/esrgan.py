@@ -251,7 +251,8 @@ def load_esrgan(path: str) -> RRDBNet:
 
 @torch.no_grad()
 def upscale_image(net: nn.Module, rgb: torch.Tensor, size=None) -> torch.Tensor:
-    """net: a 4x upscaler (RRDBNet, or models/swinir.py SwinIR).
+    """net: a 4x upscaler (RRDBNet, models/swinir.py SwinIR or models/hat.py
+    HAT).
     rgb [N, 3, H, W] in 0..1 (any float dtype, any device) -> the model's
     4x output in fp32, clamped to 0..1, on rgb's device; with size = (h, w)
     resized to it by the pipeline's Lanczos stand-in (antialiased bicubic),

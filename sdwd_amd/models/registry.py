@@ -446,10 +446,11 @@ def find_upscaler(name: Optional[str]) -> Optional[str]:
 
 
 def load_upscaler(name: str, device="cpu", dtype: Optional[torch.dtype] = None):
-    """The named upscaler (models/esrgan.py RRDBNet or models/swinir.py
-    SwinIR, told apart by the file's tensor names) on `device`, cached per
-    (file, device, dtype)."""
+    """The named upscaler (models/esrgan.py RRDBNet, models/swinir.py SwinIR
+    or models/hat.py HAT, told apart by the file's tensor names) on `device`,
+    cached per (file, device, dtype)."""
     from .esrgan import load_esrgan
+    from .hat import is_hat_state_dict, load_hat
     from .swinir import is_swinir_state_dict, load_swinir
 
     found = find_upscaler(name)
@@ -463,7 +464,10 @@ def load_upscaler(name: str, device="cpu", dtype: Optional[torch.dtype] = None):
             from safetensors import safe_open
 
             with safe_open(key[0], framework="pt") as f:
-                if is_swinir_state_dict(f.keys()):
+                # a HAT has a SwinIR's block names as well: ask for it first
+                if is_hat_state_dict(f.keys()):
+                    load = load_hat
+                elif is_swinir_state_dict(f.keys()):
                     load = load_swinir
         _upscaler_cache[key] = load(key[0]).to(device=device, dtype=dtype)
     return _upscaler_cache[key]

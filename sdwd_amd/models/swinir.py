@@ -46,7 +46,8 @@ _SUPPORTED = (
     "8, head dim <= 32, 1conv or 3conv residual connections, 3-channel "
     "input (the real-world SwinIR-M / SwinIR-L x4 models). Not supported: "
     "pixelshuffle, pixelshuffledirect (lightweight) and denoising heads, "
-    "scales other than 4, windows other than 8, head dims above 32, HAT / DAT"
+    "scales other than 4, windows other than 8, head dims above 32, DAT "
+    "(HAT: models/hat.py)"
 )
 
 

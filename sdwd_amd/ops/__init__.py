@@ -618,10 +618,11 @@ def attention_swin_supported(qkv: torch.Tensor, bias: torch.Tensor) -> bool:
     return _swin_kernel_reason(qkv, bias) is None
 
 
-def _swin_region_mask(h: int, w: int, shift: int, device) -> torch.Tensor:
-    """[windows, 64, 64]: -100 where query and key lie in different regions
-    of the shifted frame, built from the three row and three column slices."""
-    ws = SWIN_WINDOW
+def _swin_region_mask(h: int, w: int, shift: int, device,
+                      ws: int = SWIN_WINDOW) -> torch.Tensor:
+    """[windows, ws*ws, ws*ws]: -100 where query and key lie in different
+    regions of the shifted frame, built from the three row and three column
+    slices."""
     img = torch.zeros(h, w, device=device)
     cnt = 0
     for hs in (slice(0, -ws), slice(-ws, -shift), slice(-shift, None)):
@@ -693,6 +694,199 @@ def attention_swin(
             raise ValueError(f"attention_swin: {why}")
         return ext().attention_swin(qkv, bias, float(scale), shift)
     return _attention_swin_torch(qkv, bias, float(scale), shift)
+
+
+# ---------------------------------------------------------------------------
+# HAT: window-16 self-attention and overlapping cross-attention (kw 24)
+# ---------------------------------------------------------------------------
+HAT_WINDOW = 16
+_HAT_KW = (HAT_WINDOW, HAT_WINDOW * 3 // 2)
+
+
+def _hat_offset_gather(kw: int, device) -> torch.Tensor:
+    """[256, kw*kw] positions of (query, key) pairs in a flattened
+    [kw+15, kw+15] offset table: (ky - qy + 15) * R + kx - qx + 15."""
+    r = kw + HAT_WINDOW - 1
+    q = torch.arange(HAT_WINDOW, device=device)
+    k = torch.arange(kw, device=device)
+    d = k[None, :] - q[:, None] + HAT_WINDOW - 1             # [16, kw]
+    pos = d[:, None, :, None] * r + d[None, :, None, :]      # [qy, qx, ky, kx]
+    return pos.reshape(HAT_WINDOW * HAT_WINDOW, kw * kw)
+
+
+def window_bias_offsets(table: torch.Tensor, index: torch.Tensor,
+                        kw: int) -> torch.Tensor:
+    """A HAT relative-position bias as the offset table the kernel takes:
+    [heads, kw+15, kw+15], entry [ky - qy + 15, kx - qx + 15] the bias of key
+    (ky, kx) of the kw x kw key patch for query (qy, qx) of the 16 x 16 window.
+
+    table is [T, heads], index [256, kw*kw] as the model stores them (negative
+    entries address the table from its end). Each offset is read from one
+    (query, key) pair that has it; the expansion is then checked against
+    table[index] for every pair, and an index that is not translation
+    invariant raises ValueError naming the first mismatch."""
+    n = HAT_WINDOW * HAT_WINDOW
+    if kw not in _HAT_KW:
+        raise ValueError(f"window_bias_offsets: kw must be one of {_HAT_KW}")
+    if table.dim() != 2 or tuple(index.shape) != (n, kw * kw):
+        raise ValueError(
+            f"window_bias_offsets: table must be [T, heads] and index "
+            f"[{n}, {kw * kw}], got {tuple(table.shape)} and "
+            f"{tuple(index.shape)}")
+    index = index.to(table.device).long()
+    if index.min() < -table.shape[0] or index.max() >= table.shape[0]:
+        raise ValueError("window_bias_offsets: index entries outside the "
+                         f"table's {table.shape[0]} rows")
+    r = kw + HAT_WINDOW - 1
+    pos = _hat_offset_gather(kw, table.device)
+    slot = torch.empty(r * r, dtype=torch.long, device=table.device)
+    slot[pos.reshape(-1)] = index.reshape(-1)     # one pair per offset wins
+    bad = (slot[pos] != index).nonzero()
+    if bad.numel():
+        q, k = (int(v) for v in bad[0])
+        raise ValueError(
+            f"window_bias_offsets: the index is not translation invariant: "
+            f"query {q}, key {k} has entry {int(index[q, k])} but another "
+            f"pair at the same offset has {int(slot[pos[q, k]])}")
+    return table[slot].view(r, r, -1).permute(2, 0, 1).contiguous()
+
+
+def _hat_kernel_reason(qkv: torch.Tensor, bias_off: torch.Tensor
+                       ) -> Optional[str]:
+    """Why hat_attn_bf16_kernel does not take these (shape-checked)
+    arguments, or None when it does."""
+    if not (qkv.is_cuda and bias_off.is_cuda
+            and qkv.device == bias_off.device):
+        return "qkv and bias_off must be on the same GPU"
+    if qkv.dtype != torch.bfloat16:
+        return f"qkv must be bf16, got {qkv.dtype}"
+    if bias_off.dtype != torch.float32:
+        return f"bias_off must be fp32, got {bias_off.dtype}"
+    if not bias_off.is_contiguous():
+        return "bias_off must be contiguous"
+    if qkv.shape[5] != SWIN_DPAD:
+        return (f"head dim {qkv.shape[5]} must be padded to Dp = "
+                f"{SWIN_DPAD} (zero channels) by the caller")
+    if qkv.stride(5) != 1 or qkv.data_ptr() % 16 or any(
+            qkv.shape[i] != 1 and (qkv.stride(i) % 8 or qkv.stride(i) < 0)
+            for i in range(5)):
+        return ("qkv needs unit innermost stride and 16-byte-aligned head "
+                "rows (outer strides multiples of 8)")
+    return None
+
+
+def _hat_check(qkv, bias_off, shift: int, kw: int) -> None:
+    name = "attention_hat"
+    if kw not in _HAT_KW:
+        raise ValueError(f"{name}: kw must be one of {_HAT_KW}, got {kw}")
+    if qkv.dim() != 6 or qkv.shape[3] != 3:
+        raise ValueError(f"{name}: qkv must be [B, H, W, 3, heads, Dp], got "
+                         f"{tuple(qkv.shape)}")
+    b, h, w, _, heads, _ = qkv.shape
+    if b < 1 or heads < 1 or h < 1 or w < 1 or h % HAT_WINDOW or w % HAT_WINDOW:
+        raise ValueError(f"{name}: the token grid {h} x {w} must be a "
+                         f"multiple of the window ({HAT_WINDOW})")
+    r = kw + HAT_WINDOW - 1
+    if tuple(bias_off.shape) != (heads, r, r):
+        raise ValueError(f"{name}: bias_off must be [{heads}, {r}, {r}] at kw "
+                         f"{kw} (window_bias_offsets), got "
+                         f"{tuple(bias_off.shape)}")
+    if shift not in (0, HAT_WINDOW // 2) or (shift and kw != HAT_WINDOW):
+        raise ValueError(f"{name}: shift must be 0, or {HAT_WINDOW // 2} at "
+                         f"kw {HAT_WINDOW}; got shift {shift}, kw {kw}")
+    if not (qkv.is_floating_point() and bias_off.is_floating_point()):
+        raise ValueError(f"{name}: qkv and bias_off must be floating point")
+
+
+def attention_hat_supported(qkv: torch.Tensor, bias_off: torch.Tensor,
+                            kw: int = HAT_WINDOW) -> bool:
+    """True when attention_hat runs hat_attn_bf16_kernel on these arguments:
+    qkv a bf16 [B, H, W, 3, heads, 32] GPU view with unit innermost stride
+    and 16-byte-aligned head rows, H and W multiples of 16, bias_off a
+    contiguous fp32 [heads, kw+15, kw+15] on the same GPU, kw 16 or 24."""
+    try:
+        _hat_check(qkv, bias_off, 0, kw)
+    except ValueError:
+        return False
+    return _hat_kernel_reason(qkv, bias_off) is None
+
+
+def _attention_hat_torch(qkv, bias_off, scale: float, shift: int,
+                         kw: int) -> torch.Tensor:
+    """The literal definition. kw 16: roll, partition, bias and slice-built
+    mask, softmax, reverse, roll back. kw 24: partitioned queries against
+    F.unfold(kernel 24, stride 16, padding 4) of K and V. The bias is
+    bias_off expanded with one gather. Any head dim, any float dtype (bf16
+    and fp16 compute in fp32)."""
+    ws = HAT_WINDOW
+    b, h, w, _, heads, d = qkv.shape
+    nq, nwin = ws * ws, (h // ws) * (w // ws)
+    cdt = qkv.dtype if qkv.dtype in (torch.float32, torch.float64) \
+        else torch.float32
+    x = qkv.to(cdt)
+    bias = bias_off.to(cdt).flatten(1)[:, _hat_offset_gather(kw, qkv.device)]
+    if shift:
+        x = torch.roll(x, shifts=(-shift, -shift), dims=(1, 2))
+
+    def windows(t):     # [B, H, W, heads, d] -> [B, windows, heads, 256, d]
+        t = t.reshape(b, h // ws, ws, w // ws, ws, heads, d)
+        return t.permute(0, 1, 3, 5, 2, 4, 6).reshape(b, nwin, heads, nq, d)
+
+    def patches(t):     # the same, 24 x 24 patches with zeros outside
+        t = t.permute(0, 3, 4, 1, 2).reshape(b, heads * d, h, w)
+        t = F.unfold(t, kernel_size=kw, stride=ws, padding=(kw - ws) // 2)
+        return t.view(b, heads, d, kw * kw, nwin).permute(0, 4, 1, 3, 2)
+
+    q = windows(x[:, :, :, 0])
+    if kw == ws:
+        k, v = windows(x[:, :, :, 1]), windows(x[:, :, :, 2])
+    else:
+        k, v = patches(x[:, :, :, 1]), patches(x[:, :, :, 2])
+    attn = (q * scale) @ k.transpose(-2, -1) + bias[None, None]
+    if shift:
+        mask = _swin_region_mask(h, w, shift, qkv.device, ws).to(cdt)
+        attn = attn + mask[None, :, None]
+    out = torch.softmax(attn, dim=-1) @ v       # [B, windows, heads, 256, d]
+    out = out.view(b, h // ws, w // ws, heads, ws, ws, d)
+    out = out.permute(0, 1, 4, 2, 5, 3, 6).reshape(b, h, w, heads * d)
+    if shift:
+        out = torch.roll(out, shifts=(shift, shift), dims=(1, 2))
+    return out.to(qkv.dtype)
+
+
+def attention_hat(
+    qkv: torch.Tensor,
+    bias_off: torch.Tensor,
+    scale: float,
+    shift: int = 0,
+    kw: int = HAT_WINDOW,
+    native: bool = True,
+) -> torch.Tensor:
+    """HAT's attention over an un-partitioned token grid: 16 x 16 query
+    windows against their own window (kw 16, shift 0 or 8 with Swin's region
+    mask) or against the 24 x 24 patch centred on the window (kw 24, the
+    overlapping cross-attention; positions outside the grid are present keys
+    with k = v = 0).
+
+    qkv [B, H, W, 3, heads, Dp] is the QKV projection of the grid (a view of
+    the GEMM output is fine), bias_off [heads, kw+15, kw+15] the relative
+    position bias by offset (window_bias_offsets). Returns
+    [B, H, W, heads * Dp] with every query's row at its own token.
+
+    bf16 qkv on the GPU runs hat_attn_bf16_kernel (ops/hip/attention_hat.hip)
+    and must satisfy its contract (Dp = 32, contiguous fp32 bias_off, aligned
+    head rows): what it does not take raises ValueError with the reason,
+    nothing is composed silently. CPU tensors, other dtypes and native=False
+    take the literal torch definition, which the model's reference route uses.
+    """
+    shift, kw = int(shift), int(kw)
+    _hat_check(qkv, bias_off, shift, kw)
+    if native and qkv.is_cuda and qkv.dtype == torch.bfloat16:
+        why = _hat_kernel_reason(qkv, bias_off)
+        if why is not None:
+            raise ValueError(f"attention_hat: {why}")
+        return ext().attention_hat(qkv, bias_off, float(scale), shift, kw)
+    return _attention_hat_torch(qkv, bias_off, float(scale), shift, kw)
 
 
 # ---------------------------------------------------------------------------

@@ -66,17 +66,6 @@ struct SwinArgs {
 
 constexpr int SWIN_RS = 40;  // V tile row stride (bf16): 80 B, 5 16-byte slots
 
-// transposed V fragment of 16 keys from the wave's row-major tile: lane l
-// receives V[k0 + 8 * half + j][l % 32], j = 0..7 (the mapping of
-// attention_wide.hip's PV loop, decoded by tools/tr16_probe.py)
-__device__ __forceinline__ bf16x8 swin_v_frag(const __bf16 *a) {
-  const wide_bf16x4 lo =
-      __builtin_amdgcn_ds_read_tr16_b64_v4bf16((wide_lds_bf16x4 *)a);
-  const wide_bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (wide_lds_bf16x4 *)(a + 4 * SWIN_RS));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
 WIDE_KERNEL_ATTR __launch_bounds__(256, 2) __global__
 void swin_attn_bf16_kernel(const __hip_bfloat16 *__restrict__ qkv,
                            const float *__restrict__ bias,
@@ -173,7 +162,7 @@ void swin_attn_bf16_kernel(const __hip_bfloat16 *__restrict__ qkv,
     bf16x8 vf[4];  // V fragments of keys kc*16 .. +16, all 32 channels
 #pragma unroll
     for (int kc = 0; kc < 4; ++kc)
-      vf[kc] = swin_v_frag(vlane + kc * 16 * SWIN_RS);
+      vf[kc] = tr_v_frag<SWIN_RS>(vlane + kc * 16 * SWIN_RS);
     __builtin_amdgcn_wave_barrier();
 
     // the wrap straddles only the last window row / column

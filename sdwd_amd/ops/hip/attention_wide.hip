@@ -84,11 +84,6 @@ __device__ __forceinline__ void wide_mfma_settle(f32x16 &acc) {
   asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc));
 }
 
-__device__ __forceinline__ void wide_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 // O tile element *= a, in place in the AGPR it lives in. Written as plain
 // `o[d][r] *= a` the allocator moves half of O to VGPRs for the whole loop
 // and spills Q (1244 B/lane of scratch at DPAD 512). The reads are far from

@@ -17,6 +17,7 @@ static inline hipStream_t cur_stream() {
 #include "attention.hip"
 #include "attention_wide.hip"
 #include "attention_swin.hip"
+#include "attention_hat.hip"
 #include "swin_mlp.hip"
 #include "conv_v4.hip"
 #include "conv.hip"
@@ -731,6 +732,47 @@ torch::Tensor attention_swin(torch::Tensor qkv, torch::Tensor bias,
   return swin_attn_raw(qkv, bias, scale, shift);
 }
 
+torch::Tensor attention_hat(torch::Tensor qkv, torch::Tensor bias_off,
+                            double scale, long shift, long kw) {
+  // qkv [B, H, W, 3, heads, 32] view, bias_off [heads, kw + 15, kw + 15] fp32
+  // (hat_attn_bf16_kernel<kw>). Everything an address is formed from is
+  // checked here; failures raise, nothing is composed silently
+  TORCH_CHECK(kw == 16 || kw == 24, "attention_hat: kw must be 16 or 24");
+  TORCH_CHECK(qkv.dim() == 6 && qkv.size(3) == 3 && qkv.size(5) == 32,
+              "attention_hat: qkv must be [B, H, W, 3, heads, 32]");
+  TORCH_CHECK(qkv.is_cuda() && bias_off.is_cuda() &&
+                  qkv.get_device() == bias_off.get_device(),
+              "attention_hat: qkv and bias_off must be on the same GPU");
+  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16,
+              "attention_hat: qkv must be bf16");
+  TORCH_CHECK(bias_off.scalar_type() == torch::kFloat32,
+              "attention_hat: bias_off must be fp32");
+  const long B = qkv.size(0), H = qkv.size(1), W = qkv.size(2),
+             heads = qkv.size(4);
+  TORCH_CHECK(B >= 1 && heads >= 1 && H >= 16 && W >= 16 && H % 16 == 0 &&
+                  W % 16 == 0,
+              "attention_hat: the token grid ", H, " x ", W,
+              " must be a positive multiple of the window (16)");
+  TORCH_CHECK(bias_off.dim() == 3 && bias_off.size(0) == heads &&
+                  bias_off.size(1) == kw + 15 && bias_off.size(2) == kw + 15 &&
+                  bias_off.is_contiguous(),
+              "attention_hat: bias_off must be a contiguous [heads, ", kw + 15,
+              ", ", kw + 15, "]");
+  TORCH_CHECK(shift == 0 || (shift == 8 && kw == 16),
+              "attention_hat: shift must be 0, or 8 at kw 16");
+  TORCH_CHECK(heads <= 65535 && B * H * W * heads * 32 < (1L << 40) &&
+                  B * (H / 16) * (W / 16) < (1L << 31),
+              "attention_hat: problem too large");
+  bool rows16 = qkv.stride(5) == 1 && ((uintptr_t)qkv.data_ptr()) % 16 == 0;
+  for (int i = 0; i < 5; ++i)
+    rows16 = rows16 && (qkv.size(i) == 1 || qkv.stride(i) % 8 == 0) &&
+             qkv.stride(i) >= 0;
+  TORCH_CHECK(rows16,
+              "attention_hat: qkv needs unit stride in the head dim and "
+              "16-byte-aligned head rows");
+  return hat_attn_raw(qkv, bias_off, scale, shift, kw);
+}
+
 std::vector<torch::Tensor> swin_mlp(torch::Tensor x, torch::Tensor res,
                                     torch::Tensor w1p, torch::Tensor b1p,
                                     torch::Tensor w2p, torch::Tensor b2,
@@ -1006,6 +1048,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_swin", &attention_swin, py::arg("qkv"), py::arg("bias"),
         py::arg("scale"), py::arg("shift"));
   m.def("attention_swin_plan", &attention_swin_plan);
+  m.def("attention_hat", &attention_hat, py::arg("qkv"), py::arg("bias_off"),
+        py::arg("scale"), py::arg("shift"), py::arg("kw"));
   m.def("swin_mlp", &swin_mlp, py::arg("x"), py::arg("res"), py::arg("w1p"),
         py::arg("b1p"), py::arg("w2p"), py::arg("b2"),
         py::arg("ln_w") = py::none(), py::arg("ln_b") = py::none(),
