@@ -19,10 +19,12 @@ the [heads, kw+15, kw+15] offset table of ops.window_bias_offsets; nothing is
 rolled, partitioned, unfolded or masked. The MLPs run on ops.swin_mlp with
 the next norm fused, the convs at the embed width (a CAB's two convs, the
 group conv, conv_after_body, conv_before_upsample) on ops.conv_ragged, the
-tail on the 64-channel convs. Head rows are zero-padded to 32 once per
-weight version exactly as models/swinir.py does. The QKV and proj GEMMs,
-the CAB's GELU and channel attention, the three-way residual sum and
-pixel_shuffle stay on the library (TODO.md, "HAT").
+tail on the 64-channel convs. A HAB's channel attention, its three-way
+residual sum and norm2 run on ops.channel_gate and ops.gated_add_layer_norm
+(hab_tail.hip), the OCAB's residual + norm2 on ops.add_layer_norm. Head rows
+are zero-padded to 32 once per weight version exactly as models/swinir.py
+does. The QKV and proj GEMMs, the CAB's GELU and pixel_shuffle stay on the
+library (TODO.md, "HAT").
 """
 from __future__ import annotations
 
@@ -152,6 +154,23 @@ class ChannelAttention(nn.Module):
         y = F.relu(F.conv2d(y, c1.weight, c1.bias))
         return x * torch.sigmoid(F.conv2d(y, c2.weight, c2.bias))
 
+    def prepared(self):
+        """(w1 [S, C], b1 [S], w2 [C, S], b2 [C]) in fp32 for
+        ops.channel_gate, re-cast when a parameter changes (as
+        layers._fp32_cached)."""
+        c1, c2 = self.attention[1], self.attention[3]
+        src = (c1.weight, c1.bias, c2.weight, c2.bias)
+        key = tuple((t.data_ptr(), t._version) for t in src)
+        cache = getattr(self, "_fp32_cache", None)
+        if cache is None or cache[0] != key:
+            with torch.no_grad():
+                cache = (key, c1.weight.float().flatten(1).contiguous(),
+                         c1.bias.float(),
+                         c2.weight.float().flatten(1).contiguous(),
+                         c2.bias.float())
+            self._fp32_cache = cache
+        return cache[1:]
+
 
 class CAB(nn.Module):
     def __init__(self, dim: int, compress: int, squeeze: int):
@@ -230,6 +249,10 @@ class HAT(nn.Module):
     # as SwinIR.native_convs: the embed-width convs on ops.conv_ragged
     native_convs = True
     _conv_native = SwinIR._conv_native
+    # a HAB's channel attention + residual sum + norm2 and the OCAB's
+    # residual + norm2 on hab_tail.hip; False keeps them composed in torch
+    # (A/B timing)
+    fused_tail = True
 
     def __init__(self, embed_dim: int = 180, depths=(6,) * 6,
                  num_heads: int = 6, mlp_ratio: float = 2.0,
@@ -305,10 +328,12 @@ class HAT(nn.Module):
                 y = y + res
         return y
 
-    def _mlp_native(self, blk, t: torch.Tensor, nxt):
+    def _mlp_native(self, blk, t: torch.Tensor, nxt, n=None):
         """t + mlp(norm2(t)) and the following norm `nxt` of it (or None):
-        ops.swin_mlp, composed at a width it has no instantiation for."""
-        n = blk.norm2(t)
+        ops.swin_mlp, composed at a width it has no instantiation for. n is
+        norm2(t) where the fused tail has made it already."""
+        if n is None:
+            n = blk.norm2(t)
         if blk.mlp.fused and ops.swin_mlp_width_supported(t.shape[-1]):
             ln = _fp32_cached(nxt) if nxt is not None else (None, None)
             return ops.swin_mlp(n, t, *blk.mlp.prepared(), *ln,
@@ -329,12 +354,27 @@ class HAT(nn.Module):
         for j, blk in enumerate(blocks):
             cab = blk.conv_block.cab
             c = F.gelu(self._conv(cab[0], _nchw(n)))
-            c = cab[3](self._conv(cab[2], c))
-            t = t + blk.attn(n, sa, blk.shift, native=True) \
-                + CONV_SCALE * _tokens(c)
+            c = self._conv(cab[2], c)
+            attn = blk.attn(n, sa, blk.shift, native=True)
+            n2 = None
+            if self.fused_tail and ops.hab_tail_supported(t, attn, _tokens(c)) \
+                    and self.embed_dim // self.squeeze_factor \
+                    <= ops.CHANNEL_GATE_MAX_S:
+                gate = ops.channel_gate(_tokens(c), *cab[3].prepared(),
+                                        scale=CONV_SCALE)
+                t, n2 = ops.gated_add_layer_norm(
+                    t, attn, _tokens(c), gate, *_fp32_cached(blk.norm2),
+                    blk.norm2.eps)
+            else:
+                t = t + attn + CONV_SCALE * _tokens(cab[3](c))
             nxt = blocks[j + 1].norm1 if j + 1 < len(blocks) else ocab.norm1
-            t, n = self._mlp_native(blk, t, nxt)
-        t = t + ocab.attend(n, oca, 0, native=True)
+            t, n = self._mlp_native(blk, t, nxt, n2)
+        attn = ocab.attend(n, oca, 0, native=True)
+        if self.fused_tail:
+            t, n2 = ops.add_layer_norm(attn, t, *_fp32_cached(ocab.norm2),
+                                       ocab.norm2.eps)
+            return self._mlp_native(ocab, t, None, n2)[0]
+        t = t + attn
         return self._mlp_native(ocab, t, None)[0]
 
     def _forward_native(self, x: torch.Tensor) -> torch.Tensor:

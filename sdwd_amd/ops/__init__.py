@@ -144,9 +144,12 @@ def add_layer_norm(x, res, weight, bias, eps: float = 1e-5, gather=None):
 
     gather (token merging): an int32 [B, N] table, plan.slot. res is then
     the merged sequence [B, M, D] and row t of x adds res[b, gather[b, t]]:
-    the unmerge folded into the add, so the unmerged tensor never exists."""
-    if x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] % 8 == 0 \
-            and x.shape[-1] <= 1536:
+    the unmerge folded into the add, so the unmerged tensor never exists.
+
+    Without gather, a width that is a multiple of 4 but not of 8 (embed 180,
+    60), at most 256, runs the un-gated hab_tail_bf16_kernel."""
+    d = x.shape[-1]
+    if x.is_cuda and x.dtype == torch.bfloat16 and d % 8 == 0 and d <= 1536:
         if gather is not None:
             out = ext().add_layer_norm_gather(
                 x, res, weight, bias, eps, gather.contiguous()
@@ -154,6 +157,11 @@ def add_layer_norm(x, res, weight, bias, eps: float = 1e-5, gather=None):
         else:
             out = ext().add_layer_norm(x, res, weight, bias, eps)
         return out[0], out[1]
+    if gather is None and x.is_cuda and x.dtype == torch.bfloat16 \
+            and res.dtype == x.dtype and res.shape == x.shape \
+            and d % 4 == 0 and d <= HAB_TAIL_MAX_C:
+        return gated_add_layer_norm(x.contiguous(), res.contiguous(), None,
+                                    None, weight, bias, eps)
     if gather is not None:
         res = _tome_gather_rows(res, gather)
     s = (x.float() + res.float()).to(x.dtype)
@@ -1029,6 +1037,121 @@ def swin_mlp(x, res, w1, b1, w2, b2, ln_weight=None, ln_bias=None,
     if ln_weight is None:
         return s, None
     return s, F.layer_norm(s, (s.shape[-1],), ln_weight, ln_bias, eps)
+
+
+# ---------------------------------------------------------------------------
+# the elementwise tail of a HAT block: channel-attention gate, the three-way
+# residual sum and the norm behind it (ops/hip/hab_tail.hip)
+# ---------------------------------------------------------------------------
+HAB_TAIL_MAX_C = 256     # one 8-byte piece a lane: C / 4 <= 64
+CHANNEL_GATE_MAX_S = 32  # squeeze width channel_gate_kernel holds
+
+
+def _hab_rows(t: torch.Tensor) -> bool:
+    return bool(t.is_cuda and t.dtype == torch.bfloat16 and t.is_contiguous()
+                and t.data_ptr() % 8 == 0)
+
+
+def hab_tail_supported(*rows: torch.Tensor) -> bool:
+    """True when hab_tail_bf16_kernel (and, for c, channel_pool_bf16_kernel)
+    takes these token tensors: contiguous, 8-byte-aligned bf16 [..., C] of
+    one shape on one GPU, C a multiple of 4, at most 256."""
+    x = rows[0]
+    c = x.shape[-1]
+    return bool(x.numel() and all(_hab_rows(t) and t.shape == x.shape
+                    and t.device == x.device for t in rows)
+                and c % 4 == 0 and 4 <= c <= HAB_TAIL_MAX_C and have_ext())
+
+
+def _f32_gpu(t: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    """t as a contiguous, 16-byte-aligned fp32 tensor on like's device."""
+    t = t.detach().to(device=like.device, dtype=torch.float32).contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def _channel_gate_check(c, w1, b1, w2, b2) -> None:
+    if c.dim() != 4:
+        raise ValueError("channel_gate: c must be [B, H, W, C], got "
+                         f"{tuple(c.shape)}")
+    ch = c.shape[-1]
+    if ch % 4 or ch < 4:
+        raise ValueError(f"channel_gate: C = {ch} must be a multiple of 4")
+    if w1.dim() != 2 or w1.shape[1] != ch or w1.shape[0] < 1:
+        raise ValueError(f"channel_gate: w1 {tuple(w1.shape)} must be "
+                         f"[S, {ch}]")
+    s = w1.shape[0]
+    for name, t, shape in (("b1", b1, (s,)), ("w2", w2, (ch, s)),
+                           ("b2", b2, (ch,))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"channel_gate: {name} {tuple(t.shape)} must be "
+                             f"{list(shape)}")
+
+
+def channel_gate(c, w1, b1, w2, b2, scale: float = 1.0) -> torch.Tensor:
+    """The per-channel gate of a squeeze-and-excitation block over [B, H, W,
+    C] tokens: scale * sigmoid(w2 relu(w1 mean_hw(c) + b1) + b2), fp32
+    [B, C]. w1 [S, C], b1 [S], w2 [C, S], b2 [C].
+
+    Contiguous bf16 c on the GPU with C <= 256 and S <= 32 runs
+    channel_pool_bf16_kernel and channel_gate_kernel: fixed-order sums, the
+    same bits on every call. Everything else evaluates the formula in torch
+    in fp32 (the CPU route and the oracle). A malformed argument raises
+    ValueError."""
+    _channel_gate_check(c, w1, b1, w2, b2)
+    b, ch = c.shape[0], c.shape[-1]
+    if hab_tail_supported(c) and w1.shape[0] <= CHANNEL_GATE_MAX_S:
+        return ext().channel_gate(c.view(b, -1, ch), _f32_gpu(w1, c),
+                                  _f32_gpu(b1, c), _f32_gpu(w2, c),
+                                  _f32_gpu(b2, c), float(scale))
+    mean = c.float().mean((1, 2))
+    hidden = F.relu(F.linear(mean, w1.float(), b1.float()))
+    return scale * torch.sigmoid(F.linear(hidden, w2.float(), b2.float()))
+
+
+def gated_add_layer_norm(x, a, c, gate, weight, bias, eps: float = 1e-5):
+    """(s, LayerNorm(s)) with s = (x + a) + gate[b] * c over [B, H, W, C]
+    tokens, gate fp32 [B, C] (ops.channel_gate); c and gate both None gives
+    s = x + a, ops.add_layer_norm without the width limit of its kernel.
+
+    Contiguous bf16 tensors on the GPU with C % 4 == 0 and C <= 256 run
+    hab_tail_bf16_kernel: one pass, fp32 math, the norm taken from the
+    unrounded s. Everything else runs the same formula in torch, the sum
+    rounded to x's dtype before the norm as add_layer_norm's fallback does.
+    A malformed argument raises ValueError."""
+    if (c is None) != (gate is None):
+        raise ValueError("gated_add_layer_norm: give both c and gate or "
+                         "neither")
+    ch = x.shape[-1]
+    if ch % 4 or ch < 4:
+        raise ValueError(f"gated_add_layer_norm: C = {ch} must be a multiple "
+                         "of 4")
+    for name, t in (("a", a), ("c", c)):
+        if t is not None and t.shape != x.shape:
+            raise ValueError(f"gated_add_layer_norm: {name} {tuple(t.shape)} "
+                             f"must have x's shape {tuple(x.shape)}")
+    if gate is not None and (x.dim() < 2
+                             or tuple(gate.shape) != (x.shape[0], ch)):
+        raise ValueError(f"gated_add_layer_norm: gate {tuple(gate.shape)} "
+                         f"must be [{x.shape[0]}, {ch}]")
+    for name, t in (("weight", weight), ("bias", bias)):
+        if tuple(t.shape) != (ch,):
+            raise ValueError(f"gated_add_layer_norm: {name} "
+                             f"{tuple(t.shape)} must be [{ch}]")
+    rows = (x, a) if c is None else (x, a, c)
+    if hab_tail_supported(*rows):
+        hw = x.numel() // (x.shape[0] * ch) if c is not None else 1
+        out = ext().hab_tail(
+            x.view(-1, ch), a.view(-1, ch),
+            None if c is None else c.view(-1, ch),
+            None if c is None else _f32_gpu(gate, x),
+            _f32_gpu(weight, x), _f32_gpu(bias, x), eps, hw)
+        return out[0].view(x.shape), out[1].view(x.shape)
+    s = x.float() + a.float()
+    if c is not None:
+        s = s + gate.float().view(
+            (x.shape[0],) + (1,) * (x.dim() - 2) + (ch,)) * c.float()
+    s = s.to(x.dtype)
+    return s, layer_norm(s, weight, bias, eps)
 
 
 # ---------------------------------------------------------------------------

@@ -19,6 +19,7 @@ static inline hipStream_t cur_stream() {
 #include "attention_swin.hip"
 #include "attention_hat.hip"
 #include "swin_mlp.hip"
+#include "hab_tail.hip"
 #include "conv_v4.hip"
 #include "conv.hip"
 #include "conv_small.hip"
@@ -844,6 +845,112 @@ std::vector<torch::Tensor> swin_mlp(torch::Tensor x, torch::Tensor res,
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// HAB tail (hab_tail.hip)
+// ---------------------------------------------------------------------------
+static bool hab_rows_ok(const torch::Tensor &t, const torch::Tensor &like) {
+  return t.is_cuda() && t.get_device() == like.get_device() &&
+         t.scalar_type() == torch::kBFloat16 && t.is_contiguous() &&
+         ((uintptr_t)t.data_ptr()) % 8 == 0;
+}
+static bool hab_f32_ok(const torch::Tensor &t, const torch::Tensor &like,
+                       at::IntArrayRef shape) {
+  return t.is_cuda() && t.get_device() == like.get_device() &&
+         t.scalar_type() == torch::kFloat32 && t.sizes() == shape &&
+         t.is_contiguous() && ((uintptr_t)t.data_ptr()) % 16 == 0;
+}
+
+// c [B, HW, C] bf16; w1 [S, C], b1 [S], w2 [C, S], b2 [C] fp32 ->
+// gate [B, C] fp32 = scale * sigmoid(w2 relu(w1 mean_hw(c) + b1) + b2)
+// (channel_pool_bf16_kernel, channel_gate_kernel)
+torch::Tensor channel_gate(torch::Tensor c, torch::Tensor w1, torch::Tensor b1,
+                           torch::Tensor w2, torch::Tensor b2, double scale) {
+  TORCH_CHECK(c.dim() == 3 && hab_rows_ok(c, c),
+              "channel_gate: c must be a contiguous, 8-byte-aligned bf16 "
+              "[B, HW, C] on the GPU");
+  const long B = c.size(0), HW = c.size(1), C = c.size(2);
+  TORCH_CHECK(C >= 4 && C % 4 == 0 && C <= 256,
+              "channel_gate: C = ", C, " must be a multiple of 4, at most 256");
+  TORCH_CHECK(HW >= 1 && B * HW < (1L << 31) && B < 65536,
+              "channel_gate: B * HW must be below 2^31 and B below 65536");
+  TORCH_CHECK(w1.dim() == 2 && w1.size(0) >= 1 && w1.size(0) <= GATE_MAX_S,
+              "channel_gate: w1 must be [S, C] with S <= ", GATE_MAX_S);
+  const long S = w1.size(0);
+  TORCH_CHECK(hab_f32_ok(w1, c, {S, C}) && hab_f32_ok(b1, c, {S}) &&
+                  hab_f32_ok(w2, c, {C, S}) && hab_f32_ok(b2, c, {C}),
+              "channel_gate: w1 [S, C], b1 [S], w2 [C, S], b2 [C] must be "
+              "contiguous, 16-byte-aligned fp32 on c's GPU");
+  auto gate = torch::empty({B, C}, c.options().dtype(torch::kFloat));
+  if (B == 0) return gate;
+  const long P = (HW + POOL_ROWS - 1) / POOL_ROWS;
+  auto partial = torch::empty({B, P, C}, gate.options());
+  auto stream = cur_stream();
+  hipLaunchKernelGGL(channel_pool_bf16_kernel, dim3((unsigned)P, (unsigned)B),
+                     dim3(256), 0, stream,
+                     (const __hip_bfloat16 *)c.data_ptr(),
+                     partial.data_ptr<float>(), (int)C, (int)HW, (int)P);
+  hipLaunchKernelGGL(channel_gate_kernel, dim3((unsigned)B),
+                     dim3(GATE_THREADS), 0, stream, partial.data_ptr<float>(),
+                     w1.data_ptr<float>(), b1.data_ptr<float>(),
+                     w2.data_ptr<float>(), b2.data_ptr<float>(),
+                     gate.data_ptr<float>(), (int)C, (int)S, (int)P,
+                     (float)(1.0 / (double)HW), (float)scale);
+  return gate;
+}
+
+// x, a (, c) [R, C] bf16 rows, R = B * hw; gate [B, C] fp32 with c, or
+// neither -> {bf16(s), bf16(LN(s) * w + b)}, s = (x + a) + gate[row / hw] * c
+// (hab_tail_bf16_kernel)
+std::vector<torch::Tensor> hab_tail(torch::Tensor x, torch::Tensor a,
+                                    c10::optional<torch::Tensor> c,
+                                    c10::optional<torch::Tensor> gate,
+                                    torch::Tensor w, torch::Tensor b,
+                                    double eps, long hw) {
+  TORCH_CHECK(x.dim() == 2 && hab_rows_ok(x, x),
+              "hab_tail: x must be a contiguous, 8-byte-aligned bf16 [R, C] "
+              "on the GPU");
+  TORCH_CHECK(a.sizes() == x.sizes() && hab_rows_ok(a, x),
+              "hab_tail: a must be a contiguous, 8-byte-aligned bf16 tensor "
+              "of x's shape on x's GPU");
+  const long R = x.size(0), C = x.size(1);
+  TORCH_CHECK(C >= 4 && C % 4 == 0 && C <= 256,
+              "hab_tail: C = ", C, " must be a multiple of 4, at most 256");
+  TORCH_CHECK(R < (1L << 31), "hab_tail: too many rows");
+  TORCH_CHECK(c.has_value() == gate.has_value(),
+              "hab_tail: give both c and gate or neither");
+  TORCH_CHECK(hab_f32_ok(w, x, {C}) && hab_f32_ok(b, x, {C}),
+              "hab_tail: the LayerNorm weight and bias must be fp32 [C], "
+              "contiguous and 16-byte aligned");
+  if (c.has_value()) {
+    TORCH_CHECK(c->sizes() == x.sizes() && hab_rows_ok(*c, x),
+                "hab_tail: c must be a contiguous, 8-byte-aligned bf16 tensor "
+                "of x's shape on x's GPU");
+    TORCH_CHECK(hw >= 1 && R % hw == 0 && hab_f32_ok(*gate, x, {R / hw, C}),
+                "hab_tail: gate must be fp32 [R / hw, C], contiguous and "
+                "16-byte aligned, with hw dividing R");
+  }
+  std::vector<torch::Tensor> out{torch::empty_like(x), torch::empty_like(x)};
+  if (R == 0) return out;
+  const int G = C <= 64 ? 16 : C <= 128 ? 32 : 64;
+  const long rows = 4L * TAIL_ITERS * 2 * (WAVE / G);
+  dim3 grid((unsigned)((R + rows - 1) / rows)), block(256);
+  auto launch = [&](auto kern, const void *cp, const float *gp) {
+    hipLaunchKernelGGL(kern, grid, block, 0, cur_stream(),
+                       (const __hip_bfloat16 *)x.data_ptr(),
+                       (const __hip_bfloat16 *)a.data_ptr(),
+                       (const __hip_bfloat16 *)cp, gp, w.data_ptr<float>(),
+                       b.data_ptr<float>(),
+                       (__hip_bfloat16 *)out[0].data_ptr(),
+                       (__hip_bfloat16 *)out[1].data_ptr(), (int)R, (int)C,
+                       (int)(c.has_value() ? hw : 1), G, (float)eps);
+  };
+  if (c.has_value())
+    launch(hab_tail_bf16_kernel<true>, c->data_ptr(), gate->data_ptr<float>());
+  else
+    launch(hab_tail_bf16_kernel<false>, nullptr, nullptr);
+  return out;
+}
+
 torch::Tensor attention_blend_bshd(torch::Tensor q, torch::Tensor k,
                                    torch::Tensor v, torch::Tensor w,
                                    torch::Tensor kv_index,
@@ -1054,6 +1161,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("b1p"), py::arg("w2p"), py::arg("b2"),
         py::arg("ln_w") = py::none(), py::arg("ln_b") = py::none(),
         py::arg("eps") = 1e-5);
+  m.def("channel_gate", &channel_gate);
+  m.def("hab_tail", &hab_tail, py::arg("x"), py::arg("a"), py::arg("c"),
+        py::arg("gate"), py::arg("w"), py::arg("b"), py::arg("eps"),
+        py::arg("hw"));
   m.def("probe_mfma32", &probe_mfma32);
   m.def("probe_mfma16", &probe_mfma16);
   m.def("probe_tr16", &probe_tr16);
