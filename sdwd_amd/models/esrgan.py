@@ -1,4 +1,5 @@
-"""ESRGAN-family upscalers: RRDBNet (Real-ESRGAN / BasicSR definition).
+"""ESRGAN-family upscalers: RRDBNet and SRVGGNetCompact (Real-ESRGAN /
+BasicSR definitions).
 
 A 4x RRDBNet is conv_first, nb residual-in-residual dense blocks (RRDB, three
 dense blocks of five 3x3 convs each), conv_body plus the trunk residual, two
@@ -12,6 +13,14 @@ residual (and, in the third block, the RRDB's) folded into its epilogue.
 Nothing is concatenated or copied: 15 launches per RRDB. Three workspaces
 rotate, because the RRDB's input must survive until its third block's conv 5
 reads it as the outer residual.
+
+A compact model (SRVGGNetCompact: "R-ESRGAN General 4xV3", "General WDN 4xV3",
+"AnimeVideo") is a chain of 3x3 convs at one width, a per-channel PReLU after
+each, ended by a 64 -> 48 conv, PixelShuffle(4) and + nearest4x(input). On a
+bf16 GPU the stem runs on ops.conv3x3_small and every other conv on
+ops.conv_compact, whose variants absorb the stem's activation, each layer's
+PReLU, and the pixel shuffle with the nearest-4x residual: num_conv + 2
+launches, no torch op between them.
 """
 from __future__ import annotations
 
@@ -31,9 +40,11 @@ MAX_INPUT_PIXELS = 2048 * 2048
 _SUPPORTED = (
     "supported: 4x RRDBNet .safetensors with 3-channel input, new-arch keys "
     "(conv_first, body.N.rdbK.convJ, conv_body, conv_up1/2, conv_hr, "
-    "conv_last) or old-arch keys (model.0, model.1.sub.N.RDBK.convJ.0, ...). "
-    "Not supported: 1x/2x pixel-unshuffle variants, non-3-channel input, "
-    "SwinIR / HAT / compact (SRVGG) / LDSR models"
+    "conv_last) or old-arch keys (model.0, model.1.sub.N.RDBK.convJ.0, ...), "
+    "and 4x compact (SRVGGNetCompact) .safetensors with 64 features and "
+    "per-channel PReLU (body.N keys). Not supported: 1x/2x pixel-unshuffle "
+    "variants, non-3-channel input, compact models of scale 2 or 3, of "
+    "another width or with ReLU / LeakyReLU, SwinIR / HAT / LDSR models"
 )
 
 
@@ -187,6 +198,75 @@ class RRDBNet(nn.Module):
         return self._forward_plain(x)
 
 
+class SRVGGNetCompact(nn.Module):
+    """SRVGGNetCompact(nf, num_conv, scale=4): [N, 3, H, W] in 0..1 ->
+    [N, 3, 4H, 4W]. `body` is Real-ESRGAN's module list: conv, PReLU,
+    (conv, PReLU) x num_conv, conv to 3 * scale^2 channels."""
+
+    def __init__(self, nf: int = 64, num_conv: int = 16, scale: int = 4):
+        super().__init__()
+        if scale != 4:
+            raise ValueError("SRVGGNetCompact: only scale 4 is built "
+                             f"(got {scale})")
+        self.nf, self.num_conv, self.scale = nf, num_conv, scale
+        mods = [_conv(3, nf), nn.PReLU(nf)]
+        for _ in range(num_conv):
+            mods += [_conv(nf, nf), nn.PReLU(nf)]
+        mods.append(_conv(nf, 3 * scale * scale))
+        self.body = nn.ModuleList(mods)
+
+    # -- the plain route: CPU, native=False, the oracle ----------------------
+    def _forward_plain(self, x: torch.Tensor) -> torch.Tensor:
+        out = x
+        for m in self.body:
+            if isinstance(m, nn.PReLU):
+                out = F.prelu(out, m.weight)
+            else:
+                out = F.conv2d(out, m.weight, m.bias, padding=1)
+        out = F.pixel_shuffle(out, self.scale)
+        return out + F.interpolate(x, scale_factor=self.scale, mode="nearest")
+
+    # -- the native route: bf16 on the GPU -----------------------------------
+    def native_supported(self, x: torch.Tensor) -> bool:
+        """True when forward(x) runs every conv after the stem on
+        conv_compact_bf16_kernel: bf16 on the GPU at 64 features."""
+        return bool(
+            x.is_cuda and x.dtype == torch.bfloat16
+            and self.body[0].weight.dtype == torch.bfloat16
+            and ops.have_ext()
+            and self.nf == 64 and self.scale == 4 and self.num_conv >= 1
+            and ops.conv3x3_small_supported(3, self.nf)
+        )
+
+    def _forward_native(self, x: torch.Tensor) -> torch.Tensor:
+        x = x.contiguous(memory_format=torch.channels_last)
+        convs, acts = self.body[0::2], self.body[1::2]
+        stem = convs[0]
+        feat = ops.conv3x3_small(x, stem._wprep(), stem.bias)
+        pre = acts[0].weight       # the stem's PReLU, applied by the next conv
+        for conv, act in zip(convs[1:-1], acts[1:]):
+            feat = ops.conv_compact(feat, conv._wprep(), conv.bias,
+                                    slope=act.weight, pre_slope=pre)
+            pre = None
+        last = convs[-1]           # + pixel shuffle + nearest4x(x)
+        return ops.conv_compact(feat, last._wprep(), last.bias,
+                                shuffle_base=x)
+
+    def forward(self, x: torch.Tensor, native: bool = True) -> torch.Tensor:
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError("SRVGGNetCompact: x must be [N, 3, H, W], got "
+                             f"{tuple(x.shape)}")
+        if x.shape[2] * x.shape[3] > MAX_INPUT_PIXELS:
+            raise ValueError(
+                f"SRVGGNetCompact: input {x.shape[3]}x{x.shape[2]} exceeds "
+                "the whole-image limit of 2048 x 2048 pixels (tiling is not "
+                "built)"
+            )
+        if native and self.native_supported(x):
+            return self._forward_native(x)
+        return self._forward_plain(x)
+
+
 # old-arch (ESRGAN "model.N") names -> new-arch names; nb is the index of the
 # trunk conv inside model.1.sub
 _OLD_RDB = re.compile(r"^model\.1\.sub\.(\d+)\.RDB(\d)\.conv(\d)\.0\.(weight|bias)$")
@@ -213,11 +293,58 @@ def _rename_old_arch(state: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return out
 
 
-def esrgan_from_state_dict(state: Dict[str, torch.Tensor]) -> RRDBNet:
-    """Build an RRDBNet from a state dict under either key naming; nf, gc and
-    nb are inferred from the tensors."""
-    state = {k[len("params_ema."):] if k.startswith("params_ema.") else k: v
-             for k, v in state.items()}
+_COMPACT_KEY = re.compile(r"^body\.(\d+)\.(weight|bias)$")
+
+
+def _compact_from_state_dict(state: Dict[str, torch.Tensor]) -> SRVGGNetCompact:
+    """Real-ESRGAN's SRVGGNetCompact layout: body.0 the stem conv, odd body.k
+    the PReLU slopes, the last body.k the 3 * scale^2 conv; nf, num_conv and
+    scale are inferred from the tensors."""
+    for key in state:
+        if not _COMPACT_KEY.match(key):
+            raise ValueError(f"load_esrgan: unknown tensor '{key}'; "
+                             + _SUPPORTED)
+    stem = state["body.0.weight"]
+    last_k = max(int(_COMPACT_KEY.match(k)[1]) for k in state)
+    last = state.get(f"body.{last_k}.weight")
+    if stem.dim() != 4 or tuple(stem.shape[1:]) != (3, 3, 3):
+        raise ValueError("load_esrgan: the compact model's stem is not a 3x3 "
+                         "conv of 3 channels; " + _SUPPORTED)
+    nf = stem.shape[0]
+    slopes = state.get("body.1.weight")
+    if slopes is None or slopes.dim() != 1 or slopes.numel() != nf:
+        raise ValueError(
+            "load_esrgan: the compact model's activation is not a "
+            "per-channel PReLU (ReLU / LeakyReLU variant); " + _SUPPORTED)
+    if last_k % 2 or last_k < 2 or last is None or last.dim() != 4:
+        raise ValueError("load_esrgan: the compact model does not end in a "
+                         "conv; " + _SUPPORTED)
+    scale = round((last.shape[0] / 3) ** 0.5)
+    if 3 * scale * scale != last.shape[0] or scale != 4:
+        raise ValueError(
+            f"load_esrgan: compact model with {last.shape[0]} output "
+            "channels (scale is not 4); " + _SUPPORTED)
+    if nf != 64:
+        raise ValueError(f"load_esrgan: compact model with {nf} features; "
+                         + _SUPPORTED)
+    net = SRVGGNetCompact(nf=nf, num_conv=(last_k - 2) // 2, scale=scale)
+    try:
+        net.load_state_dict(state, strict=True)
+    except RuntimeError as exc:
+        raise ValueError(f"load_esrgan: {exc}; " + _SUPPORTED) from None
+    return net.eval()
+
+
+def esrgan_from_state_dict(state: Dict[str, torch.Tensor]) -> nn.Module:
+    """Build an RRDBNet (either key naming; nf, gc and nb inferred from the
+    tensors) or, when there is no conv_first and the body.N tensors are a
+    compact model's, an SRVGGNetCompact."""
+    for prefix in ("params_ema.", "params."):
+        state = {k[len(prefix):] if k.startswith(prefix) else k: v
+                 for k, v in state.items()}
+    if "conv_first.weight" not in state and "body.0.weight" in state and (
+            "body.1.weight" not in state or state["body.1.weight"].dim() == 1):
+        return _compact_from_state_dict(state)
     if any(k.startswith("model.") for k in state):
         state = _rename_old_arch(state)
     first = state.get("conv_first.weight")
@@ -239,8 +366,9 @@ def esrgan_from_state_dict(state: Dict[str, torch.Tensor]) -> RRDBNet:
     return net.eval()
 
 
-def load_esrgan(path: str) -> RRDBNet:
-    """Load an ESRGAN-family upscaler from a .safetensors file."""
+def load_esrgan(path: str) -> nn.Module:
+    """Load an ESRGAN-family upscaler (RRDBNet or SRVGGNetCompact) from a
+    .safetensors file."""
     if not str(path).endswith(".safetensors"):
         raise ValueError(f"load_esrgan: '{path}' is not a .safetensors file; "
                          + _SUPPORTED)
@@ -251,8 +379,8 @@ def load_esrgan(path: str) -> RRDBNet:
 
 @torch.no_grad()
 def upscale_image(net: nn.Module, rgb: torch.Tensor, size=None) -> torch.Tensor:
-    """net: a 4x upscaler (RRDBNet, models/swinir.py SwinIR or models/hat.py
-    HAT).
+    """net: a 4x upscaler (RRDBNet, SRVGGNetCompact, models/swinir.py SwinIR
+    or models/hat.py HAT).
     rgb [N, 3, H, W] in 0..1 (any float dtype, any device) -> the model's
     4x output in fp32, clamped to 0..1, on rgb's device; with size = (h, w)
     resized to it by the pipeline's Lanczos stand-in (antialiased bicubic),

@@ -411,8 +411,9 @@ def upscaler_dir() -> str:
 
 
 def refresh_upscaler_files(dirpath: Optional[str] = None) -> list:
-    """Scan the upscaler directory for *.safetensors ESRGAN-family models
-    (the host's ESRGAN / RealESRGAN model folders). The file stem is the
+    """Scan the upscaler directory for *.safetensors upscaler models (the
+    host's ESRGAN / RealESRGAN / SwinIR / HAT model folders; RRDBNet and
+    compact SRVGG files alike). The file stem is the
     upscaler's name as hr_upscaler / upscaler_1 give it."""
     import os
 
@@ -446,9 +447,9 @@ def find_upscaler(name: Optional[str]) -> Optional[str]:
 
 
 def load_upscaler(name: str, device="cpu", dtype: Optional[torch.dtype] = None):
-    """The named upscaler (models/esrgan.py RRDBNet, models/swinir.py SwinIR
-    or models/hat.py HAT, told apart by the file's tensor names) on `device`,
-    cached per (file, device, dtype)."""
+    """The named upscaler (models/esrgan.py RRDBNet or SRVGGNetCompact,
+    models/swinir.py SwinIR or models/hat.py HAT, told apart by the file's
+    tensor names) on `device`, cached per (file, device, dtype)."""
     from .esrgan import load_esrgan
     from .hat import is_hat_state_dict, load_hat
     from .swinir import is_swinir_state_dict, load_swinir

@@ -2219,6 +2219,139 @@ def conv_ragged(
 
 
 # ---------------------------------------------------------------------------
+# weight-stationary 3x3 conv at Cin 64 with a per-channel PReLU or a
+# pixel-shuffle epilogue (the compact Real-ESRGAN upscalers, models/esrgan.py)
+# ---------------------------------------------------------------------------
+_CU_COUNT: dict = {}
+
+
+def _cu_count(device) -> int:
+    idx = torch.device(device).index
+    idx = torch.cuda.current_device() if idx is None else idx
+    if idx not in _CU_COUNT:
+        _CU_COUNT[idx] = int(
+            torch.cuda.get_device_properties(idx).multi_processor_count)
+    return _CU_COUNT[idx]
+
+
+def conv_compact_supported(x, w_prep) -> bool:
+    """True when conv_compact runs conv_compact_bf16_kernel on these tensors:
+    bf16 on the GPU, x [N, 64, H, W] channels_last with a 16-byte-aligned
+    base and N * H * W * 64 < 2^31, w_prep a contiguous [64 or 48, 3, 3, 64].
+    The routing predicate."""
+    return bool(
+        x.is_cuda and w_prep.is_cuda
+        and x.dtype == w_prep.dtype == torch.bfloat16
+        and x.dim() == w_prep.dim() == 4
+        and x.shape[1] == 64 and min(x.shape) >= 1
+        and tuple(w_prep.shape[1:]) == (3, 3, 64)
+        and w_prep.shape[0] in (48, 64)
+        and x.is_contiguous(memory_format=torch.channels_last)
+        and w_prep.is_contiguous()
+        and x.data_ptr() % 16 == 0 and w_prep.data_ptr() % 16 == 0
+        and x.numel() < 2 ** 31
+    )
+
+
+def conv_compact(
+    x: torch.Tensor,
+    w_prep: torch.Tensor,
+    bias: Optional[torch.Tensor],
+    slope: Optional[torch.Tensor] = None,
+    pre_slope: Optional[torch.Tensor] = None,
+    shuffle_base: Optional[torch.Tensor] = None,
+    blocks: Optional[int] = None,
+) -> torch.Tensor:
+    """A 3x3 / pad 1 / stride 1 conv of the compact (SRVGG) upscalers, with
+    one of two epilogues; exactly one of `slope` and `shuffle_base` is given.
+
+    slope [Cout]:  y = prelu(conv3x3(x', w) + bias, slope), [N, Cout, H, W]
+    channels_last. With pre_slope [Cin], x' = prelu(x, pre_slope) rounded to
+    x's dtype, as the separate activation pass it replaces would have stored
+    it; otherwise x' = x.
+
+    shuffle_base [N, 3, H, W] (any strides):  y = pixel_shuffle(conv3x3(x, w)
+    + bias, 4) + nearest4x(shuffle_base), [N, 3, 4H, 4W] contiguous; Cout is
+    48. The sum is formed before the one rounding.
+
+    w_prep is [Cout, 3, 3, Cin]. GPU, conv_compact_supported(x, w_prep):
+    conv_compact_bf16_kernel (ops/hip/conv_compact.hip), the layer's weights
+    resident in LDS while a block walks output tiles, fp32 accumulate, one
+    rounding; `blocks` caps the grid (default: the CU count). CPU, or when
+    the predicate is false: the same formula with F.conv2d (fp32 math for
+    bf16). A bad argument raises ValueError naming it.
+    """
+    name = "conv_compact"
+    for nm, t in (("x", x), ("w_prep", w_prep)):
+        if not torch.is_tensor(t) or t.dim() != 4:
+            raise ValueError(f"{name}: {nm} must be a 4-d tensor")
+    n, cin, h, w = x.shape
+    cout = w_prep.shape[0]
+    if min(n, cin, h, w) < 1:
+        raise ValueError(f"{name}: x must be non-empty, got {tuple(x.shape)}")
+    if tuple(w_prep.shape) != (cout, 3, 3, cin):
+        raise ValueError(
+            f"{name}: w_prep must be [Cout,3,3,Cin] = {(cout, 3, 3, cin)}, "
+            f"got {tuple(w_prep.shape)}"
+        )
+    if (slope is None) == (shuffle_base is None):
+        raise ValueError(f"{name}: exactly one of slope and shuffle_base "
+                         "must be given")
+    if pre_slope is not None and slope is None:
+        raise ValueError(f"{name}: pre_slope needs the slope epilogue")
+    for nm, t, length in (("bias", bias, cout), ("slope", slope, cout),
+                          ("pre_slope", pre_slope, cin)):
+        if t is not None and (not torch.is_tensor(t) or t.dim() != 1
+                              or t.numel() != length):
+            raise ValueError(f"{name}: {nm} must be a vector of {length} "
+                             "values")
+    if shuffle_base is not None:
+        if cout != 48:
+            raise ValueError(f"{name}: the shuffle_base epilogue is "
+                             f"PixelShuffle(4) of 48 channels, w_prep has "
+                             f"{cout}")
+        if (not torch.is_tensor(shuffle_base)
+                or tuple(shuffle_base.shape) != (n, 3, h, w)):
+            raise ValueError(f"{name}: shuffle_base must be {(n, 3, h, w)}")
+    for nm, t in (("w_prep", w_prep), ("bias", bias), ("slope", slope),
+                  ("pre_slope", pre_slope), ("shuffle_base", shuffle_base)):
+        if t is None:
+            continue
+        if t.device != x.device:
+            raise ValueError(f"{name}: {nm} is on {t.device}, x on {x.device}")
+        if nm in ("w_prep", "shuffle_base") and t.dtype != x.dtype:
+            raise ValueError(f"{name}: {nm} is {t.dtype}, x is {x.dtype}")
+    if blocks is not None and (not isinstance(blocks, int) or blocks < 1):
+        raise ValueError(f"{name}: blocks must be a positive int or None")
+
+    if conv_compact_supported(x, w_prep) and cout == (
+            48 if slope is None else 64):
+        def vec(t):  # the kernel reads fp32 or bf16 as stored
+            if t is None or (t.is_contiguous() and t.dtype in (
+                    torch.float32, torch.bfloat16)):
+                return t
+            return t.float().contiguous()
+
+        return ext().conv_compact(
+            x, w_prep, vec(bias), vec(slope), vec(pre_slope), shuffle_base,
+            int(blocks) if blocks is not None else _cu_count(x.device),
+        )
+    wide = x.dtype == torch.bfloat16
+    up = (lambda t: t.float()) if wide else (lambda t: t)
+    xin = up(x)
+    if pre_slope is not None:
+        xin = up(F.prelu(xin, pre_slope.to(xin.dtype)).to(x.dtype))
+    y = F.conv2d(xin, up(w_prep).permute(0, 3, 1, 2),
+                 None if bias is None else bias.to(xin.dtype), padding=1)
+    if slope is not None:
+        y = F.prelu(y, slope.to(y.dtype)).to(x.dtype)
+        return y.contiguous(memory_format=torch.channels_last)
+    y = F.pixel_shuffle(y, 4) + F.interpolate(
+        up(shuffle_base), scale_factor=4, mode="nearest")
+    return y.to(x.dtype).contiguous()
+
+
+# ---------------------------------------------------------------------------
 # timestep embedding (sinusoidal)
 # ---------------------------------------------------------------------------
 def timestep_embedding(

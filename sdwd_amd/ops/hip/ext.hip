@@ -25,6 +25,7 @@ static inline hipStream_t cur_stream() {
 #include "conv_small.hip"
 #include "conv_dense.hip"
 #include "conv_ragged.hip"
+#include "conv_compact.hip"
 #include "rng.hip"
 #include "tome.hip"
 
@@ -1193,4 +1194,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias"), py::arg("out"), py::arg("ksize"), py::arg("res"),
         py::arg("lrelu"), py::arg("slope"));
   m.def("conv_ragged_supported_widths", &conv_ragged_supported_widths);
+  m.def("conv_compact", &conv_compact, py::arg("x"), py::arg("w_prep"),
+        py::arg("bias"), py::arg("slope"), py::arg("pre_slope"),
+        py::arg("shuffle_base"), py::arg("blocks"));
 }

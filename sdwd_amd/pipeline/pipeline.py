@@ -574,8 +574,8 @@ class StableDiffusionPipeline:
         """Pixel-space hires handoff (sdwui non-"Latent" hr_upscalers):
         decode the base latents, upscale the uint8 pixels (the PIL round
         trip sdwui performs), re-encode per image (shard-invariant,
-        seeded). A name found in SDWD_UPSCALER_DIR runs that model (RRDBNet,
-        models/esrgan.py, SwinIR, models/swinir.py, or HAT, models/hat.py)
+        seeded). A name found in SDWD_UPSCALER_DIR runs that model (RRDBNet or
+        SRVGGNetCompact, models/esrgan.py, SwinIR, models/swinir.py, or HAT, models/hat.py)
         on the decoded image;
         any other model-based name falls back to bicubic-antialiased with a
         warning."""
