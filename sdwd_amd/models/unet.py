@@ -368,8 +368,8 @@ class BasicTransformerBlock(nn.Module):
         # path). The pipeline sets it on the level-0 blocks only.
         self.tome_ratio = 0.0
 
-    # token merging on the GPU: True runs the tome.hip kernels (match, merge,
-    # gathered add+LN); False keeps the torch-composed route (A/B timing,
+    # token merging on the GPU: True runs the tome.hip kernels (match, plan,
+    # merge, gathered add+LN); False keeps the torch-composed route (A/B timing,
     # comparison tests). The CPU takes the torch route either way.
     tome_native = True
 
@@ -383,7 +383,8 @@ class BasicTransformerBlock(nn.Module):
             node_max, node_idx = ops.tome_match(x, h, w)
         else:
             node_max, node_idx = ops.tome_match(x.float(), h, w)
-        return ops.tome_plan(node_max, node_idx, h, w, r)
+        return ops.tome_plan(node_max, node_idx, h, w, r,
+                             native=self.tome_native)
 
     def forward(self, x, context, hw=None, window=None):
         """window = (gh, gw, th, tw): Hypertile windows of the self-

@@ -170,7 +170,8 @@ def add_layer_norm(x, res, weight, bias, eps: float = 1e-5, gather=None):
 
 # ---------------------------------------------------------------------------
 # token merging (ToMe) for the level-0 self-attention: 2x2 partition, cosine
-# match, plan, merge, unmerge. Kernels in ops/hip/tome.hip; every op has a
+# match, plan, merge, unmerge. Kernels in ops/hip/tome.hip and
+# ops/hip/tome_plan.hip; every op has a
 # plain torch path (CPU route, oracle, and the composed GPU route for widths
 # and dtypes without a kernel). docs/kernels.md has the definition.
 # ---------------------------------------------------------------------------
@@ -289,12 +290,31 @@ class TomePlan:
         return (self.slot, self.unm_tok, self.seg_start, self.members)
 
 
-def tome_plan(node_max, node_idx, h: int, w: int, r: int) -> TomePlan:
+def tome_plan_supported(node_max, node_idx, h: int, w: int) -> bool:
+    """True when tome_plan runs tome_plan_kernel on these inputs: contiguous
+    fp32 / int32 GPU tensors [B, Ns] of a grid of at most 16384 tokens
+    (128 x 128), which the kernel keeps in LDS as one row."""
+    return bool(
+        node_max.is_cuda and node_idx.is_cuda
+        and node_max.dtype == torch.float32 and node_idx.dtype == torch.int32
+        and node_max.dim() == 2 and node_idx.dim() == 2
+        and node_max.is_contiguous() and node_idx.is_contiguous()
+        and int(h) * int(w) <= ext().tome_plan_max_tokens()
+    )
+
+
+def tome_plan(node_max, node_idx, h: int, w: int, r: int,
+              native: bool = True) -> TomePlan:
     """Select the r src tokens with the largest node_max (ties to the lower
-    src position) and lay out the merge. Torch integer ops with static
-    shapes on node_max's device, the same on CPU and GPU: two stable sorts,
-    a cumsum, a searchsorted and scatters to unique (or discarded) targets.
-    No host sync, no atomics, so it captures into a hipGraph."""
+    src position) and lay out the merge.
+
+    GPU, tome_plan_supported(...): one launch of tome_plan_kernel. Larger
+    grids, the CPU, and native=False (the oracle of the kernel and the
+    composed route for comparisons): torch integer ops with static shapes on
+    node_max's device, two stable sorts, a cumsum, a searchsorted and
+    scatters to unique (or discarded) targets. The two routes return equal
+    tensors. No host sync, no global atomics, so both capture into a
+    hipGraph."""
     src, dst, inv = _tome_partition_all(h, w, node_max.device)
     ns, nd = src.numel(), dst.numel()
     bsz = node_max.shape[0]
@@ -303,6 +323,12 @@ def tome_plan(node_max, node_idx, h: int, w: int, r: int) -> TomePlan:
         raise ValueError(f"tome_plan: node_max/node_idx must be [B, {ns}]")
     if not 0 <= r <= ns:
         raise ValueError(f"tome_plan: r must lie in [0, {ns}] (got {r})")
+    if native and tome_plan_supported(node_max, node_idx, h, w):
+        slot, unm_tok, seg_start, members = ext().tome_plan(
+            node_max, node_idx, src, dst, r
+        )
+        return TomePlan(int(h), int(w), r, slot, unm_tok, seg_start, members,
+                        dst)
     dev = node_max.device
     nu = ns - r
     pos = torch.arange(ns, device=dev)

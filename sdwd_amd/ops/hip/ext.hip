@@ -28,6 +28,7 @@ static inline hipStream_t cur_stream() {
 #include "conv_compact.hip"
 #include "rng.hip"
 #include "tome.hip"
+#include "tome_plan.hip"
 
 #define CHECK_IN(x)                                                     \
   TORCH_CHECK(x.is_cuda(), #x " must be on GPU");                        \
@@ -456,6 +457,51 @@ std::vector<torch::Tensor> tome_match(torch::Tensor x, torch::Tensor src_tok,
                      node_max.data_ptr<float>(), (int *)node_idx.data_ptr(),
                      (int)N, (int)Ns, (int)Nd);
   return {node_max, node_idx};
+}
+
+// the largest token grid tome_plan_kernel takes (tome_plan.hip)
+long tome_plan_max_tokens() { return TP_MAX_TOKENS; }
+
+// node_max fp32 [B,Ns], node_idx int32 [B,Ns]; src_tok [Ns], dst_tok [Nd] ->
+// (slot [B,N], unm_tok [B,Ns-r], seg_start [B,Nd+1], members [B,r]), int32
+std::vector<torch::Tensor> tome_plan(torch::Tensor node_max,
+                                     torch::Tensor node_idx,
+                                     torch::Tensor src_tok,
+                                     torch::Tensor dst_tok, long r) {
+  TORCH_CHECK(node_max.is_cuda() && node_max.dim() == 2 &&
+                  node_max.is_contiguous() &&
+                  node_max.scalar_type() == torch::kFloat,
+              "tome_plan: node_max must be a contiguous fp32 [B,Ns] GPU "
+              "tensor");
+  check_tome_table(node_idx, node_max, "node_idx");
+  check_tome_table(src_tok, node_max, "src_tok");
+  check_tome_table(dst_tok, node_max, "dst_tok");
+  const long B = node_max.size(0), Ns = src_tok.numel(),
+             Nd = dst_tok.numel();
+  const long N = Ns + Nd;
+  TORCH_CHECK(node_max.size(1) == Ns && node_idx.dim() == 2 &&
+                  node_idx.size(0) == B && node_idx.size(1) == Ns,
+              "tome_plan: node_max/node_idx must be [B,", Ns, "]");
+  TORCH_CHECK(Ns >= 1 && Nd >= 1 && N <= tome_plan_max_tokens(),
+              "tome_plan: no kernel for ", N, " tokens (at most ",
+              tome_plan_max_tokens(), ")");
+  TORCH_CHECK(r >= 0 && r <= Ns, "tome_plan: r must lie in [0, ", Ns, "]");
+  TORCH_CHECK(B < (1L << 31), "tome_plan: B < 2^31");
+  auto iopt = node_max.options().dtype(torch::kInt);
+  auto slot = torch::empty({B, N}, iopt);
+  auto unm_tok = torch::empty({B, Ns - r}, iopt);
+  auto seg_start = torch::empty({B, Nd + 1}, iopt);
+  auto members = torch::empty({B, r}, iopt);
+  if (B == 0) return {slot, unm_tok, seg_start, members};
+  hipLaunchKernelGGL(tome_plan_kernel, dim3((unsigned)B), dim3(TP_THREADS), 0,
+                     cur_stream(), node_max.data_ptr<float>(),
+                     (const int *)node_idx.data_ptr(),
+                     (const int *)src_tok.data_ptr(),
+                     (const int *)dst_tok.data_ptr(), (int *)slot.data_ptr(),
+                     (int *)unm_tok.data_ptr(), (int *)seg_start.data_ptr(),
+                     (int *)members.data_ptr(), (int)N, (int)Ns, (int)Nd,
+                     (int)r);
+  return {slot, unm_tok, seg_start, members};
 }
 
 // x bf16 [B,N,C]; dst_tok [Nd]; unm_tok [B,Nu]; seg_start [B,Nd+1];
@@ -1133,6 +1179,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("add_layer_norm_gather", &add_layer_norm_gather);
   m.def("tome_match_supported_width", &tome_match_supported_width);
   m.def("tome_match", &tome_match);
+  m.def("tome_plan_max_tokens", &tome_plan_max_tokens);
+  m.def("tome_plan", &tome_plan);
   m.def("tome_merge", &tome_merge);
   m.def("tome_unmerge", &tome_unmerge);
   m.def("row_softmax_", &row_softmax_);

@@ -4,8 +4,9 @@
 // into Nd dst tokens (even row, even column) and Ns src tokens (the rest);
 // src_tok / dst_tok list their token positions in ascending order. The
 // kernels here are the float side of the feature; the integer plan (which
-// src tokens merge, the CSR of every dst's members) is torch integer ops on
-// the results of the match (ops/__init__.py, tome_plan).
+// src tokens merge, the CSR of every dst's members) is tome_plan.hip's
+// kernel on the results of the match, defined by the torch integer ops of
+// ops/__init__.py, tome_plan.
 //
 //  * tome_rnorm_bf16_kernel: 1/|x_t| = rsqrt(max(sum x^2, 2^-80)) for every
 //    token, one wave per row, fp32. The match reads the dst entries (a

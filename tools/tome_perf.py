@@ -6,7 +6,9 @@ Per block: BasicTransformerBlock at C=320, H=8 heads, batch 16, N=4096
 is timed native (tome.hip kernels) and composed (torch route), alternating,
 after a warm-up; one sample is at least --sample-seconds of work between two
 device events. The native route is also split into match / plan / merge /
-attn1 / add+LN, each stage timed alone on the tensors of a real forward.
+attn1 / add+LN, each stage timed alone on the tensors of a real forward;
+the plan is timed on both routes (plan: tome_plan_kernel, plan_torch: the
+torch route, native=False), alternating like every other pair here.
 "overhead" is match + plan + merge plus what the gathered add+LN costs over
 the plain one at ratio 0: everything token merging adds around attn1.
 
@@ -105,6 +107,8 @@ def block_case(side, ratio, args):
                 "match": lambda: ops.tome_match(x, side, side),
                 "plan": lambda: ops.tome_plan(node_max, node_idx, side,
                                               side, r),
+                "plan_torch": lambda: ops.tome_plan(node_max, node_idx, side,
+                                                    side, r, native=False),
                 "merge": lambda: ops.tome_merge(n1, plan),
                 "attn1": lambda: blk.attn1(merged),
                 "add_ln": lambda: ops.add_layer_norm(
@@ -124,8 +128,10 @@ def block_case(side, ratio, args):
             return call
 
         split = _timed({k: run(v) for k, v in stages.items()}, args)
-    for name, (med, _) in split.items():
+    for name, (med, spread) in split.items():
         row[f"{name}_ms"] = round(med, 4)
+        if name.startswith("plan"):
+            row[f"{name}_spread"] = round(spread, 4)
     line = "  ".join(f"{k} {row[f'{k}_ms']:8.4f}" for k in split)
     comp = f"  composed {row['composed_ms']:8.4f}" if ratio > 0 else ""
     print(f"N={n:<6d} ratio {ratio:<5} block {row['native_ms']:8.4f} ms "
