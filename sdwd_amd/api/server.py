@@ -960,17 +960,19 @@ def create_app(engine: Optional[LocalEngine] = None,
 
             name = find_upscaler(str(body.get("upscaler_1")))
             if name is not None:
-                # a model from SDWD_UPSCALER_DIR: 4x once, then the Lanczos
-                # entry resizes to the requested size, as hires fix does
+                # a model from SDWD_UPSCALER_DIR: run once (4x, or 1x for
+                # SCUNet), then the Lanczos entry resizes to the requested
+                # size, as hires fix does
                 from ..models.esrgan import upscale_image
 
                 pipe = next(iter(engine.pipes.values()))
                 net = load_upscaler(name, pipe.device, pipe.dtype)
+                src_h = x.shape[2]
                 try:
                     x = upscale_image(net, x / 255.0) * 255.0
                 except ValueError as exc:
                     raise HTTPException(422, str(exc))
-                scale = scale / 4.0
+                scale = scale * src_h / x.shape[2]
                 m, aa = mode_map["lanczos"]
         kwargs: Dict[str, Any] = {"mode": m}
         if aa:

@@ -380,9 +380,9 @@ def load_esrgan(path: str) -> nn.Module:
 @torch.no_grad()
 def upscale_image(net: nn.Module, rgb: torch.Tensor, size=None) -> torch.Tensor:
     """net: a 4x upscaler (RRDBNet, SRVGGNetCompact, models/swinir.py SwinIR
-    or models/hat.py HAT).
+    or models/hat.py HAT) or the 1x models/scunet.py SCUNet.
     rgb [N, 3, H, W] in 0..1 (any float dtype, any device) -> the model's
-    4x output in fp32, clamped to 0..1, on rgb's device; with size = (h, w)
+    output in fp32, clamped to 0..1, on rgb's device; with size = (h, w)
     resized to it by the pipeline's Lanczos stand-in (antialiased bicubic),
     as the host upscales past the target and resizes down."""
     p = next(net.parameters())

@@ -412,7 +412,7 @@ def upscaler_dir() -> str:
 
 def refresh_upscaler_files(dirpath: Optional[str] = None) -> list:
     """Scan the upscaler directory for *.safetensors upscaler models (the
-    host's ESRGAN / RealESRGAN / SwinIR / HAT model folders; RRDBNet and
+    host's ESRGAN / RealESRGAN / SwinIR / HAT / ScuNET model folders; RRDBNet and
     compact SRVGG files alike). The file stem is the
     upscaler's name as hr_upscaler / upscaler_1 give it."""
     import os
@@ -448,10 +448,11 @@ def find_upscaler(name: Optional[str]) -> Optional[str]:
 
 def load_upscaler(name: str, device="cpu", dtype: Optional[torch.dtype] = None):
     """The named upscaler (models/esrgan.py RRDBNet or SRVGGNetCompact,
-    models/swinir.py SwinIR or models/hat.py HAT, told apart by the file's
-    tensor names) on `device`, cached per (file, device, dtype)."""
+    models/swinir.py SwinIR, models/hat.py HAT or models/scunet.py SCUNet,
+    told apart by the file's tensor names) on `device`, cached per (file, device, dtype)."""
     from .esrgan import load_esrgan
     from .hat import is_hat_state_dict, load_hat
+    from .scunet import is_scunet_state_dict, load_scunet
     from .swinir import is_swinir_state_dict, load_swinir
 
     found = find_upscaler(name)
@@ -470,6 +471,8 @@ def load_upscaler(name: str, device="cpu", dtype: Optional[torch.dtype] = None):
                     load = load_hat
                 elif is_swinir_state_dict(f.keys()):
                     load = load_swinir
+                elif is_scunet_state_dict(f.keys()):
+                    load = load_scunet
         _upscaler_cache[key] = load(key[0]).to(device=device, dtype=dtype)
     return _upscaler_cache[key]
 

@@ -1066,6 +1066,194 @@ def swin_mlp(x, res, w1, b1, w2, b2, ln_weight=None, ln_bias=None,
 
 
 # ---------------------------------------------------------------------------
+# the window-attention half of a Swin-Conv block (SCUNet): LN1, QKV, biased
+# and masked window attention, proj, residual and LN2 in one kernel
+# ---------------------------------------------------------------------------
+WINDOW_BLOCK_WIDTHS = (32, 64)  # mirrors ext().window_block_attn_supported_width
+WINDOW_BLOCK_HEAD = 32
+
+
+def window_attn_block_prepare(wqkv: torch.Tensor, wproj: torch.Tensor):
+    """The QKV weight [3C, C] and the proj weight [C, C] (nn.Linear layout)
+    as window_block_attn_bf16_kernel stages them: flat, one contiguous 1 KB
+    block per MFMA fragment, block (tile, step) holding
+    w[32 tile + lane % 32][16 step + 8 (lane // 32) + j] at [lane][j].
+    Callers cache the pair per weight version."""
+    if wproj.dim() != 2 or wproj.shape[0] != wproj.shape[1] \
+            or tuple(wqkv.shape) != (3 * wproj.shape[0], wproj.shape[0]):
+        raise ValueError(
+            f"window_attn_block_prepare: wqkv {tuple(wqkv.shape)} and wproj "
+            f"{tuple(wproj.shape)} are not [3C, C] and [C, C]")
+    c = wproj.shape[0]
+    if c not in WINDOW_BLOCK_WIDTHS:
+        raise ValueError(f"window_attn_block_prepare: C = {c} must be one of "
+                         f"{WINDOW_BLOCK_WIDTHS}")
+
+    def frag(w):
+        return w.detach().view(w.shape[0] // 32, 32, c // 16, 2, 8).permute(
+            0, 2, 3, 1, 4).contiguous().view(-1)
+
+    return frag(wqkv), frag(wproj)
+
+
+def _wb_view_reason(name: str, t: torch.Tensor) -> Optional[str]:
+    if t.stride(3) != 1 or t.data_ptr() % 16 or any(
+            t.shape[i] != 1 and (t.stride(i) % 8 or t.stride(i) < 0)
+            for i in range(3)):
+        return (f"{name} needs unit channel stride, 16-byte-aligned rows and "
+                "pixel strides that are multiples of 8")
+    return None
+
+
+def _wb_kernel_reason(x, y_out, n2_out) -> Optional[str]:
+    """Why window_block_attn_bf16_kernel does not take these views, or None
+    when it does."""
+    if x.dim() != 4:
+        return f"x must be [B, H, W, C], got {tuple(x.shape)}"
+    if not (x.is_cuda and x.dtype == torch.bfloat16):
+        return f"x must be bf16 on the GPU, got {x.dtype} on {x.device}"
+    b, h, w, c = x.shape
+    if c not in WINDOW_BLOCK_WIDTHS:
+        return (f"C = {c} must be one of {WINDOW_BLOCK_WIDTHS} (the weights "
+                "stay in LDS; wider branches run composed)")
+    if b < 1 or h < 8 or w < 8 or h % 8 or w % 8:
+        return f"the token grid {h} x {w} must be a multiple of the window (8)"
+    for name, t in (("x", x), ("y_out", y_out), ("n2_out", n2_out)):
+        if t.shape != x.shape or t.dtype != x.dtype or t.device != x.device:
+            return f"{name} must be a bf16 {tuple(x.shape)} on x's GPU"
+        why = _wb_view_reason(name, t)
+        if why is not None:
+            return why
+    views = [t.permute(0, 3, 1, 2) for t in (x, y_out, n2_out)]
+    if any(_dense_overlap(views[i], views[j]) != "disjoint"
+           for i, j in ((1, 0), (2, 0), (1, 2))):
+        return "x, y_out and n2_out must not share memory"
+    return None
+
+
+def window_attn_block_supported(x, y_out, n2_out) -> bool:
+    """True when window_attn_block runs window_block_attn_bf16_kernel on
+    these: bf16 [B, H, W, C] views on one GPU, C 32 or 64, H and W multiples
+    of 8, unit channel stride, 16-byte-aligned rows, pixel strides that are
+    multiples of 8 (channel slices of NHWC buffers qualify), no shared
+    memory. The routing predicate."""
+    return _wb_kernel_reason(x, y_out, n2_out) is None
+
+
+def _window_attn_block_torch(x, ln1_w, ln1_b, wqkv, bqkv, rel, wproj, bproj,
+                             ln2_w, ln2_b, scale, shift, eps):
+    """The literal definition (SCUNet's WMSA between its two norms): roll,
+    partition, rel gathered by `relation`, an -inf mask filled by slices,
+    softmax, reverse, roll back."""
+    p = SWIN_WINDOW
+    b, h, w, c = x.shape
+    heads = c // WINDOW_BLOCK_HEAD
+    t = F.layer_norm(x, (c,), ln1_w, ln1_b, eps)
+    if shift:
+        t = torch.roll(t, shifts=(-shift, -shift), dims=(1, 2))
+    hw, ww = h // p, w // p
+    t = t.view(b, hw, p, ww, p, c).permute(0, 1, 3, 2, 4, 5)
+    t = t.reshape(b, hw * ww, p * p, c)
+    qkv = F.linear(t, wqkv, bqkv).view(b, hw * ww, p * p, 3 * heads, -1)
+    q, k, v = qkv.permute(3, 0, 1, 2, 4).chunk(3, dim=0)   # [heads, b, nw, 64, d]
+    sim = torch.einsum("hbwpc,hbwqc->hbwpq", q, k) * scale
+    coord = torch.tensor([[i, j] for i in range(p) for j in range(p)],
+                         device=x.device)
+    relation = coord[:, None, :] - coord[None, :, :] + p - 1
+    sim = sim + rel.to(sim.dtype)[:, relation[:, :, 0],
+                                  relation[:, :, 1]][:, None, None]
+    if shift:
+        mask = torch.zeros(hw, ww, p, p, p, p, dtype=torch.bool,
+                           device=x.device)
+        s = p - shift
+        mask[-1, :, :s, :, s:, :] = True
+        mask[-1, :, s:, :, :s, :] = True
+        mask[:, -1, :, :s, :, s:] = True
+        mask[:, -1, :, s:, :, :s] = True
+        sim = sim.masked_fill(mask.view(1, 1, hw * ww, p * p, p * p),
+                              float("-inf"))
+    o = torch.einsum("hbwij,hbwjc->hbwic", torch.softmax(sim, dim=-1), v)
+    o = o.permute(1, 2, 3, 0, 4).reshape(b, hw * ww, p * p, c)
+    o = F.linear(o, wproj, bproj).view(b, hw, ww, p, p, c)
+    o = o.permute(0, 1, 3, 2, 4, 5).reshape(b, h, w, c)
+    if shift:
+        o = torch.roll(o, shifts=(shift, shift), dims=(1, 2))
+    y = x + o
+    return y, F.layer_norm(y, (c,), ln2_w, ln2_b, eps)
+
+
+def window_attn_block(x, ln1_w, ln1_b, wqkv, bqkv, rel, wproj, bproj, ln2_w,
+                      ln2_b, scale: float, shift: int = 0, eps: float = 1e-5,
+                      out=None, native: bool = True):
+    """(y, LN2(y)) with y = x + proj(window_attention(LN1(x))): the attention
+    half of a Swin-Conv block over a [B, H, W, C] token grid, windows 8 x 8,
+    heads of 32 channels, shift 0 or 4, rel [heads, 15, 15] read by the
+    offset of key from query. QKV output channels are (t * heads + h) * 32 + c.
+
+    bf16 x on the GPU with native=True runs window_block_attn_bf16_kernel
+    (ops/hip/window_block.hip) on wqkv and wproj as
+    window_attn_block_prepare leaves them, with fp32 vectors and rel; out is
+    an optional (y, n2) pair of views to write. What the kernel does not take
+    raises ValueError with the reason; nothing is composed silently. CPU
+    tensors, other dtypes and native=False take the literal torch definition
+    on the unprepared nn.Linear weights."""
+    name = "window_attn_block"
+    shift = int(shift)
+    if x.dim() != 4:
+        raise ValueError(f"{name}: x must be [B, H, W, C], got "
+                         f"{tuple(x.shape)}")
+    b, h, w, c = x.shape
+    if shift not in (0, SWIN_WINDOW // 2):
+        raise ValueError(f"{name}: shift must be 0 or {SWIN_WINDOW // 2}, got "
+                         f"{shift}")
+    if c % WINDOW_BLOCK_HEAD or c < WINDOW_BLOCK_HEAD:
+        raise ValueError(f"{name}: C = {c} must be a multiple of the head "
+                         f"dim ({WINDOW_BLOCK_HEAD})")
+    if h < 1 or w < 1 or h % SWIN_WINDOW or w % SWIN_WINDOW:
+        raise ValueError(f"{name}: the token grid {h} x {w} must be a "
+                         f"multiple of the window ({SWIN_WINDOW})")
+    heads = c // WINDOW_BLOCK_HEAD
+    if tuple(rel.shape) != (heads, 15, 15):
+        raise ValueError(f"{name}: rel must be [heads, 15, 15] = "
+                         f"[{heads}, 15, 15], got {tuple(rel.shape)}")
+    if native and x.is_cuda and x.dtype == torch.bfloat16:
+        if out is None:
+            out = (torch.empty(x.shape, dtype=x.dtype, device=x.device),
+                   torch.empty(x.shape, dtype=x.dtype, device=x.device))
+        y, n2 = out
+        why = _wb_kernel_reason(x, y, n2)
+        if why is None and not (
+                wqkv.dtype == wproj.dtype == torch.bfloat16
+                and wqkv.dim() == wproj.dim() == 1
+                and wqkv.numel() == 3 * c * c and wproj.numel() == c * c):
+            why = ("wqkv and wproj must be the flat bf16 pair of "
+                   "window_attn_block_prepare")
+        if why is None:
+            for nm, t, n in (("ln1_w", ln1_w, c), ("ln1_b", ln1_b, c),
+                             ("bqkv", bqkv, 3 * c), ("bproj", bproj, c),
+                             ("ln2_w", ln2_w, c), ("ln2_b", ln2_b, c),
+                             ("rel", rel, heads * 225)):
+                if t.dtype != torch.float32 or t.numel() != n \
+                        or not t.is_contiguous() or t.device != x.device:
+                    why = f"{nm} must be contiguous fp32 of {n} values on x's GPU"
+                    break
+        if why is not None:
+            raise ValueError(f"{name}: {why}")
+        ext().window_block_attn(x, y, n2, ln1_w, ln1_b, wqkv, bqkv, rel, wproj,
+                                bproj, ln2_w, ln2_b, float(scale), shift,
+                                float(eps))
+        return y, n2
+    y, n2 = _window_attn_block_torch(x, ln1_w, ln1_b, wqkv, bqkv, rel, wproj,
+                                     bproj, ln2_w, ln2_b, float(scale), shift,
+                                     float(eps))
+    if out is not None:
+        out[0].copy_(y)
+        out[1].copy_(n2)
+        return out
+    return y, n2
+
+
+# ---------------------------------------------------------------------------
 # the elementwise tail of a HAT block: channel-attention gate, the three-way
 # residual sum and the norm behind it (ops/hip/hab_tail.hip)
 # ---------------------------------------------------------------------------

@@ -17,6 +17,7 @@ static inline hipStream_t cur_stream() {
 #include "attention.hip"
 #include "attention_wide.hip"
 #include "attention_swin.hip"
+#include "window_block.hip"
 #include "attention_hat.hip"
 #include "swin_mlp.hip"
 #include "hab_tail.hip"
@@ -780,6 +781,76 @@ torch::Tensor attention_swin(torch::Tensor qkv, torch::Tensor bias,
   return swin_attn_raw(qkv, bias, scale, shift);
 }
 
+void window_block_attn(torch::Tensor x, torch::Tensor y_out,
+                       torch::Tensor n2_out, torch::Tensor g1, torch::Tensor b1,
+                       torch::Tensor wqkv_p, torch::Tensor bqkv,
+                       torch::Tensor rel, torch::Tensor wp_p, torch::Tensor bp,
+                       torch::Tensor g2, torch::Tensor b2, double scale,
+                       long shift, double eps) {
+  // x, y_out, n2_out [B, H, W, C] bf16 views, C 32 or 64; wqkv_p [3C * C],
+  // wp_p [C * C] bf16 as ops.window_attn_block_prepare leaves them; the
+  // vectors and rel [C / 32, 15, 15] fp32 (window_block_attn_bf16_kernel).
+  // Everything an address is formed from is checked here; failures raise,
+  // nothing is composed silently
+  TORCH_CHECK(x.dim() == 4 && x.is_cuda() &&
+                  x.scalar_type() == torch::kBFloat16,
+              "window_block_attn: x must be a bf16 [B, H, W, C] GPU tensor");
+  const long B = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  TORCH_CHECK(window_block_attn_supported_width(C),
+              "window_block_attn: C = ", C, " must be 32 or 64");
+  TORCH_CHECK(B >= 1 && H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0,
+              "window_block_attn: the token grid ", H, " x ", W,
+              " must be a positive multiple of the window (8)");
+  TORCH_CHECK(shift == 0 || shift == 4,
+              "window_block_attn: shift must be 0 or 4");
+  TORCH_CHECK(B * (H / 8) * (W / 8) < (1L << 31),
+              "window_block_attn: problem too large");
+  auto view_ok = [&](const torch::Tensor &t) {
+    bool ok = t.is_cuda() && t.get_device() == x.get_device() &&
+              t.scalar_type() == torch::kBFloat16 && t.sizes() == x.sizes() &&
+              t.stride(3) == 1 && ((uintptr_t)t.data_ptr()) % 16 == 0;
+    long span = 0;
+    for (int i = 0; ok && i < 3; ++i) {
+      ok = t.size(i) == 1 || (t.stride(i) % 8 == 0 && t.stride(i) >= 0);
+      span += (t.size(i) - 1) * t.stride(i);
+    }
+    return ok && span < (1L << 40);
+  };
+  TORCH_CHECK(view_ok(x) && view_ok(y_out) && view_ok(n2_out),
+              "window_block_attn: x, y_out and n2_out must be bf16 "
+              "[B, H, W, C] views of one shape on one GPU with unit channel "
+              "stride, 16-byte-aligned rows and strides that are multiples "
+              "of 8");
+  auto vec_ok = [&](const torch::Tensor &t, long n) {
+    return t.is_cuda() && t.get_device() == x.get_device() &&
+           t.scalar_type() == torch::kFloat32 && t.numel() == n &&
+           t.is_contiguous();
+  };
+  TORCH_CHECK(vec_ok(g1, C) && vec_ok(b1, C) && vec_ok(g2, C) &&
+                  vec_ok(b2, C) && vec_ok(bp, C) && vec_ok(bqkv, 3 * C),
+              "window_block_attn: the norm vectors and bp must be contiguous "
+              "fp32 [C] and bqkv fp32 [3C] on x's GPU");
+  TORCH_CHECK(rel.dim() == 3 && rel.size(0) == C / 32 && rel.size(1) == 15 &&
+                  rel.size(2) == 15 && vec_ok(rel, C / 32 * 225),
+              "window_block_attn: rel must be a contiguous fp32 [", C / 32,
+              ", 15, 15] on x's GPU");
+  auto w_ok = [&](const torch::Tensor &t, long n) {
+    return t.is_cuda() && t.get_device() == x.get_device() &&
+           t.scalar_type() == torch::kBFloat16 && t.numel() == n &&
+           t.is_contiguous() && ((uintptr_t)t.data_ptr()) % 16 == 0;
+  };
+  TORCH_CHECK(w_ok(wqkv_p, 3 * C * C) && w_ok(wp_p, C * C),
+              "window_block_attn: wqkv_p and wp_p must be contiguous, "
+              "16-byte-aligned bf16 of 3C*C and C*C elements "
+              "(window_attn_block_prepare)");
+  if (C == 32)
+    window_block_launch<32>(x, y_out, n2_out, g1, b1, wqkv_p, bqkv, rel, wp_p,
+                            bp, g2, b2, scale, shift, eps);
+  else
+    window_block_launch<64>(x, y_out, n2_out, g1, b1, wqkv_p, bqkv, rel, wp_p,
+                            bp, g2, b2, scale, shift, eps);
+}
+
 torch::Tensor attention_hat(torch::Tensor qkv, torch::Tensor bias_off,
                             double scale, long shift, long kw) {
   // qkv [B, H, W, 3, heads, 32] view, bias_off [heads, kw + 15, kw + 15] fp32
@@ -1204,6 +1275,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_swin", &attention_swin, py::arg("qkv"), py::arg("bias"),
         py::arg("scale"), py::arg("shift"));
   m.def("attention_swin_plan", &attention_swin_plan);
+  m.def("window_block_attn", &window_block_attn, py::arg("x"),
+        py::arg("y_out"), py::arg("n2_out"), py::arg("g1"), py::arg("b1"),
+        py::arg("wqkv_p"), py::arg("bqkv"), py::arg("rel"), py::arg("wp_p"),
+        py::arg("bp"), py::arg("g2"), py::arg("b2"), py::arg("scale"),
+        py::arg("shift"), py::arg("eps"));
+  m.def("window_block_attn_supported_width",
+        &window_block_attn_supported_width);
+  m.def("window_block_attn_plan", &window_block_attn_plan);
   m.def("attention_hat", &attention_hat, py::arg("qkv"), py::arg("bias_off"),
         py::arg("scale"), py::arg("shift"), py::arg("kw"));
   m.def("swin_mlp", &swin_mlp, py::arg("x"), py::arg("res"), py::arg("w1p"),

@@ -575,8 +575,8 @@ class StableDiffusionPipeline:
         decode the base latents, upscale the uint8 pixels (the PIL round
         trip sdwui performs), re-encode per image (shard-invariant,
         seeded). A name found in SDWD_UPSCALER_DIR runs that model (RRDBNet or
-        SRVGGNetCompact, models/esrgan.py, SwinIR, models/swinir.py, or HAT, models/hat.py)
-        on the decoded image;
+        SRVGGNetCompact, models/esrgan.py, SwinIR, models/swinir.py, HAT, models/hat.py, or the 1x SCUNet,
+        models/scunet.py) on the decoded image;
         any other model-based name falls back to bicubic-antialiased with a
         warning."""
         key = (req.hr_upscaler or "").lower()
@@ -586,8 +586,8 @@ class StableDiffusionPipeline:
             from ..models.registry import find_upscaler, load_upscaler
 
             if find_upscaler(req.hr_upscaler) is not None:
-                # a model from SDWD_UPSCALER_DIR: 4x once, then down (or up)
-                # to the target with the Lanczos entry, as the host does
+                # a model from SDWD_UPSCALER_DIR: once (4x; SCUNet 1x), then
+                # down (or up) to the target with the Lanczos entry, as the host does
                 model = load_upscaler(req.hr_upscaler, self.device, self.dtype)
                 m, aa = _PIXEL_HR_MODES["lanczos"]
         if key not in _PIXEL_HR_MODES and model is None:
